@@ -311,8 +311,9 @@ def run_dry_exchange(args, rank, world):
     return 0 if ok else 1
 
 
-def measure(model, cfg, args, dev, rank, job, P, gen, batch, plan="throughput", steps=None, warmup=None, strong=False):
-    """time `steps` steps of the hot path at `batch` images per forward call through `job`; returns (seconds, step_fn)"""
+def measure(model, cfg, args, dev, rank, job, P, gen, batch, plan="throughput", steps=None, warmup=None, strong=False, keep=None):
+    """time `steps` steps of the hot path at `batch` images per forward call through `job`; returns (seconds, step_fn).
+    keep: a dict that receives, as host arrays, what the LAST timed step handed its caller (see dump_arrays)"""
     from groma_amd import synth
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
@@ -326,20 +327,34 @@ def measure(model, cfg, args, dev, rank, job, P, gen, batch, plan="throughput", 
     chunks = [(lo, min(lo + batch, job.rows)) for lo in range(0, job.rows, batch)]
     width = job.row_shape[0]
 
+    last_timed = warmup + steps - 1
+    held = {}   # device tensors of the last timed step (references only: copied to the host after the timed region)
+
     def step(i):
         torch.manual_seed(1000 + i)  # the path draws torch.randperm (T4)
+        hold = keep is not None and i == last_timed
         rows = []
         for lo, hi in chunks:
             if gen:
                 g = model.generate(ids[lo:hi], images=images[lo:hi], max_new_tokens=args.new_tokens, return_dict_in_generate=True,
                                    output_hidden_states=True)
                 rows.append(pack_rows(g.sequences.float(), g.hidden_states[0][-1]["pred_boxes"]))
+                if hold:
+                    held.setdefault("sequences", []).append(g.sequences)
+                    held.setdefault("pred_boxes", []).extend(g.hidden_states[0][-1]["pred_boxes"])
             else:
                 out = model.forward(input_ids=ids[lo:hi], images=images[lo:hi], use_cache=False, return_dict=True)
                 rows.append(pack_rows(out.logits[:, -1, r0:r0 + 100], out.hidden_states[1]["pred_boxes"]))
+                if hold:
+                    held.setdefault("logits", []).append(out.logits)
+                    held.setdefault("pred_boxes", []).extend(out.hidden_states[1]["pred_boxes"])
         if not rows:   # a rank whose shard is empty (global batch < world): it still takes part in the collective
-            return job.exchange(torch.zeros((0, width), dtype=torch.float32, device=dev))
-        return job.exchange(rows[0] if len(rows) == 1 else torch.cat(rows))
+            res = job.exchange(torch.zeros((0, width), dtype=torch.float32, device=dev))
+        else:
+            res = job.exchange(rows[0] if len(rows) == 1 else torch.cat(rows))
+        if hold:
+            held["rows"] = res
+        return res
 
     old = model.gemm_plan
     model.gemm_plan = plan
@@ -353,12 +368,50 @@ def measure(model, cfg, args, dev, rank, job, P, gen, batch, plan="throughput", 
         for i in range(job.setup_steps):
             step(-1 - i)
         elapsed = job.timed(step, warmup, steps, after_warmup=lambda: mark.update(c=caps()))
+        if keep is not None:   # before any further step: graph replays reuse their output buffers
+            keep.update(dump_arrays(held))
+            held.clear()
     finally:
         model.gemm_plan = old
     # a hipGraph capture (GraphPool: third sighting of a shape) inside the timed region would put a capture pass and a
     # stream sync into the measurement: counted, reported, and 0 whenever warmup >= GraphPool.CAPTURE_AT
     job.captures_in_timed_region = caps() - mark.get("c", caps())
     return elapsed, step
+
+
+DUMP_LOGITS_SAMPLE = 1 << 21   # logits elements kept per dump (all images together): 8 MB of float32
+DUMP_LAST_ROWS = 128            # images whose last-position logits are kept whole (128 x 32114 x 4 B = 16 MB)
+
+
+def dump_arrays(held):
+    """Host float32 / float64 copies of what one step handed its caller, at most ~36 MB whatever the batch:
+      rows           [global_batch, head + 401]  the step's exchanged rows (region logits or generated ids | boxes | N_i)
+      pred_boxes     [images, max N_i, 4]        the selected boxes of every image, zero padded; n_regions [images] holds N_i
+      logits_last    [min(images, 128), V]       forward: the last position's logits, whole
+      logits_sample  [images, k]                 forward: the logits at k fixed flat positions of every image's [L, V] block,
+      logits_sample_index [k]                    listed (float64) in logits_sample_index; drawn by numpy's default_rng(0)
+      sequences      [images, P + new tokens]    generate: the token ids (float64, exact)"""
+    import numpy as np
+    out = {"rows": held["rows"].float().cpu().numpy()}
+    boxes = held.get("pred_boxes", [])
+    n = [int(b.shape[0]) for b in boxes]
+    pb = np.zeros((len(boxes), max(n, default=0), 4), dtype=np.float32)
+    for i, b in enumerate(boxes):
+        pb[i, : n[i]] = b.float().cpu().numpy().reshape(-1, 4)
+    out["pred_boxes"], out["n_regions"] = pb, np.asarray(n, dtype=np.float32)
+    if "logits" in held:
+        lg = held["logits"]
+        images = sum(x.shape[0] for x in lg)
+        block = min(x.shape[1] * x.shape[2] for x in lg)   # (every image of the benchmark has the same [L, V]; else the common prefix)
+        k = min(block, max(1, DUMP_LOGITS_SAMPLE // max(images, 1)))
+        idx = np.sort(np.random.default_rng(0).choice(block, size=k, replace=False))
+        t_idx = torch.from_numpy(idx).to(lg[0].device)
+        out["logits_sample"] = torch.cat([x.reshape(x.shape[0], -1)[:, t_idx].float() for x in lg]).cpu().numpy()
+        out["logits_sample_index"] = idx.astype(np.float64)
+        out["logits_last"] = torch.cat([x[:, -1, :].float() for x in lg])[:DUMP_LAST_ROWS].cpu().numpy()
+    if "sequences" in held:
+        out["sequences"] = torch.cat(held["sequences"]).cpu().numpy().astype(np.float64)
+    return out
 
 
 def launch_roofline(m, step, n, kind):
@@ -734,6 +787,9 @@ def main():
     ap.add_argument("--host-glue", action="store_true",
                     help="with --dry-exchange: every rank also runs the forward's real host-side glue (CPU-RNG shuffles, placeholder "
                          "splice, scatter-row lists) per step and the JSON reports its microseconds per step under N-way host contention")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step handed its caller as DIR/<name>.npy (float32 / float64, rank 0, <= 64 MB; "
+                         "a fixed sample of the full logits: see dump_arrays) -- the inputs are seeded, so two builds compare output for output")
     ap.add_argument("--dry-exchange", action="store_true",
                     help="launcher / process-group / exchange / timing path only, with synthetic rows on CPU (gloo); no model")
     args = ap.parse_args()
@@ -788,7 +844,13 @@ def main():
     if gen:
         model.generation_config.eos_token_id = None  # random-init weights: fixed-length decode, never an early stop
 
-    elapsed, step = measure(model, cfg, args, dev, rank, job, P, gen, args.batch, plan=args.gemm_plan, strong=strong)
+    dumped = {} if args.dump_outputs and rank == 0 else None
+    elapsed, step = measure(model, cfg, args, dev, rank, job, P, gen, args.batch, plan=args.gemm_plan, strong=strong, keep=dumped)
+    if dumped is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     gathered = step(args.warmup + args.steps)  # one more (untimed) step: what the exchange delivered
     exchanged_regions = int(gathered[:, -1].sum().item())
     model.gemm_plan = args.gemm_plan
@@ -886,6 +948,10 @@ def main():
                      "e2e_algorithmic_tflops_per_gpu": fl["total"] * job.rows * args.steps / elapsed / 1e12,
                      "e2e_frac_of_peak": fl["total"] * job.rows * args.steps / elapsed / 1e12 / peak},
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "step": args.warmup + args.steps - 1,
+                               "arrays": {k: [str(a.dtype)] + list(a.shape) for k, a in dumped.items()},
+                               "bytes": sum(a.nbytes for a in dumped.values())}
     if vit_recs is not None:
         out["roofline"]["vit_pair_gemms"] = pair_block(vit_recs, args.steps)
     if gen:  # configs[3]: the decode steps stream the bf16 weights once per token -> HBM roofline of the GEMV kernel

@@ -135,6 +135,14 @@ def _open(path, operand):
         raise RuntimeError(
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(groma_amd has no CPU / eager fallback by design)")
+    # torch BEFORE the library: torch ships its own HIP runtime (torch/lib/libamdhip64.so, same soname), and the library must bind
+    # that one.  Loaded first, it would pull in the system runtime and the process would hold two HIP runtimes, so the library's
+    # launches would not run on the runtime torch's tensors live in (the layout probe below fails that way).
+    try:
+        import torch
+        has_gpu = torch.cuda.is_available()
+    except Exception:
+        has_gpu = False
     lib = ctypes.CDLL(path)
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
@@ -147,11 +155,6 @@ def _open(path, operand):
     # The float64-accumulating proposer GEMM (csrc/gemm_f32.hip) asks the hardware once which accumulator element holds which output
     # row of v_mfma_f64_16x16x4_f64.  Ask NOW, at load time, so that the probe (a tiny launch + a stream sync) can never fall into a
     # hipGraph capture; an unexpected answer fails here, loudly, instead of at the first proposer launch.
-    try:
-        import torch
-        has_gpu = torch.cuda.is_available()
-    except Exception:
-        has_gpu = False
     if has_gpu:
         probe = getattr(lib, "gr_diag_mfma64_rowmap", None)
         if probe is not None:
