@@ -63,6 +63,7 @@ SIGNATURES = {
     "gr_gemm_yield": [_I],
     "gr_gemm_bf16": [ctypes.POINTER(GemmDesc), _P],
     "gr_gemv_fused": [ctypes.POINTER(GemvDesc), _P],
+    "gr_gemv_fused_paged": [ctypes.POINTER(GemvDesc), _P, _I, _P],
     "gr_gemm_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _P],
     "gr_quant_rows_fp8": [_P, _I, _P, _P, _I, _I, _L, _P],
     "gr_norm_fp8": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P],
@@ -71,6 +72,9 @@ SIGNATURES = {
     "gr_attention_bf16": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _I, _L, _P, _P, _P],
     "gr_qkv_split": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P],
     "gr_decode_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _I, _I, _P, _P],
+    "gr_decode_attention_paged": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _F, _P, _I, _I, _P, _P],
+    "gr_qkv_split_paged": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P],
+    "gr_kv_scatter_pages": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "gr_resize_h_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "gr_resize_v_norm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "gr_cv2_resize_norm": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],

@@ -3,6 +3,7 @@
 // consumer fused in); what is left between the weight streams is this kernel: the 128-query-row MFMA attention tile (1 useful
 // row) replaced by a one-block-per-(row, head) dot-product kernel, optionally over key slices that the o-proj stream merges.
 //   gr_decode_attention   : softmax(q K^T * scale) V over the cache, one block per (row, head[, key slice])
+//   gr_decode_attention_paged : the same over a paged cache (64-position pages reached through a per-row block table)
 // Positions come from device memory when pos_dev is given (hipGraph replay / ragged continuous batching).
 #include "gr_common.h"
 #include "../../include/groma_hip.h"
@@ -20,19 +21,26 @@
 // DS = blocks per (row, head[, key slice]) along the OUTPUT dims (round 4): every block computes all scores and the soft-max of its
 // keys, but only HD / DS rows of V^T.  At 4 rows x 32 heads that is 256 blocks on 256 CUs instead of 128, each streaming 224 KB
 // instead of 300 KB, and -- unlike key slices -- nothing to merge: a block writes its dims of the context directly.
-template <int HD, int DS>
+//
+// PAGED (the continuous batcher's paged cache): k is a pool [pages, H, 64, HD], vt a pool [pages, H, HD, 64], and key s of row b
+// lives in page table[b * table_ld + s / 64] at offset s % 64; kv_stride is then the row's capacity (table_ld * 64), to which the
+// visible length is clamped.  The row's table (<= DEC_SMAX / 64 ints) is staged in LDS behind the scores when the block starts.  Key
+// slices start on 64-aligned keys and an 8-key chunk starts on a multiple of 8, so neither crosses a page.
+template <int HD, int DS, bool PAGED = false>
 __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                                const bf16_t* __restrict__ vt, bf16_t* __restrict__ out,
                                                                const int* __restrict__ kv_len, int H, int kv_stride,
                                                                int q_pos0, float scale, const int* __restrict__ pos_dev,
-                                                               int pos_stride, float* __restrict__ ws) {
-  extern __shared__ float sc[];  // [round_up(S, 64)] scores -> probabilities
+                                                               int pos_stride, float* __restrict__ ws,
+                                                               const int* __restrict__ table, int table_ld, int sc_len) {
+  extern __shared__ float sc[];  // [round_up(S, 64)] scores -> probabilities (PAGED: then the row's table at sc + sc_len)
   __shared__ float red[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int bh = blockIdx.x, b = bh / H;
   const int nsplit = gridDim.y, z = blockIdx.y;
   int Sall = (pos_dev ? pos_dev[b * pos_stride] : q_pos0) + 1;
   if (kv_len) Sall = min(Sall, kv_len[b]);
+  if constexpr (PAGED) Sall = min(Sall, kv_stride);
   // this block's slice of the keys (64-aligned start so the 16-B V^T loads stay aligned)
   const int chunk = (((Sall + nsplit - 1) / nsplit) + 63) & ~63;
   const int sb = z * chunk;
@@ -40,6 +48,17 @@ __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __
   const int Spad = (S + 63) & ~63;
   const bf16_t* Kp = k + ((long)bh * kv_stride + sb) * HD;
   const bf16_t* Vp = vt + (long)bh * HD * kv_stride + sb;
+  int* tbl = (int*)(sc + sc_len);
+  if constexpr (PAGED) {
+    const int np = (Sall + 63) >> 6;
+    for (int i = tid; i < np; i += 1024) tbl[i] = table[(long)b * table_ld + i];
+    __syncthreads();
+  }
+  // PAGED: 16-B chunk of K row s (this slice's numbering) at dims j8.., and of V^T row d at keys s0..s0+7
+  auto kpage = [&](int s, int j8) -> const bf16_t* {
+    const int a = sb + s;
+    return k + (((long)tbl[a >> 6] * H + (bh - b * H)) * 64 + (a & 63)) * HD + j8;
+  };
 
   // All global loads of a round are issued before anything consumes them (one exposed memory latency per round of
   // DEC_U x 64 keys, for K and for V^T together): a decode block is a pure latency chain otherwise.
@@ -50,6 +69,10 @@ __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __
   const int j = tid % LPK, g = tid / LPK;
   const int d = (int)blockIdx.z * HDB + tid / TPD, part = tid % TPD;
   const bf16_t* vrow = Vp + (long)d * kv_stride;
+  auto vpage = [&](int s0) -> const bf16_t* {
+    const int a = sb + s0;
+    return vt + (((long)tbl[a >> 6] * H + (bh - b * H)) * HD + d) * 64 + (a & 63);
+  };
   const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   float qf[8];
   {
@@ -61,7 +84,8 @@ __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __
 #pragma unroll
   for (int u = 0; u < DEC_U; ++u) {
     const int s0 = part * 8 + u * TPD * 8;
-    vv[u] = s0 < Spad ? *(const bf16x8*)(vrow + s0) : zero8;
+    if constexpr (PAGED) vv[u] = s0 < Spad ? *(const bf16x8*)vpage(s0) : zero8;
+      else vv[u] = s0 < Spad ? *(const bf16x8*)(vrow + s0) : zero8;
   }
   float mloc = -1e30f;
   for (int r0 = 0; r0 < Spad; r0 += KPI * DEC_U) {
@@ -69,7 +93,8 @@ __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __
 #pragma unroll
     for (int u = 0; u < DEC_U; ++u) {
       const int s = r0 + u * KPI + g;
-      kv[u] = s < S ? *(const bf16x8*)(Kp + (long)s * HD + j * 8) : zero8;
+      if constexpr (PAGED) kv[u] = s < S ? *(const bf16x8*)kpage(s, j * 8) : zero8;
+      else kv[u] = s < S ? *(const bf16x8*)(Kp + (long)s * HD + j * 8) : zero8;
     }
 #pragma unroll
     for (int u = 0; u < DEC_U; ++u) {
@@ -118,7 +143,8 @@ __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __
 #pragma unroll
     for (int u = 0; u < DEC_U; ++u) {
       const int s0 = r0 + part * 8 + u * TPD * 8;
-      vv[u] = s0 < Spad ? *(const bf16x8*)(vrow + s0) : zero8;
+      if constexpr (PAGED) vv[u] = s0 < Spad ? *(const bf16x8*)vpage(s0) : zero8;
+      else vv[u] = s0 < Spad ? *(const bf16x8*)(vrow + s0) : zero8;
     }
 #pragma unroll
     for (int u = 0; u < DEC_U; ++u) {
@@ -154,11 +180,36 @@ extern "C" int gr_decode_attention(const void* q, const void* k, const void* vt,
 #define LAUNCH_DA(HDV, DSV)                                                                                                    \
   hipLaunchKernelGGL((decode_attention_kernel<HDV, DSV>), dim3(B * H, nsplit, DSV), dim3(1024), lds, stream, (const bf16_t*)q, \
                      (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)out, kv_len, H, kv_stride, q_pos0, scale, pos_dev,         \
-                     pos_stride, parts)
+                     pos_stride, parts, nullptr, 0, 0)
   if (head_dim == 128) { if (ds == 2) LAUNCH_DA(128, 2); else LAUNCH_DA(128, 1); }
   else if (head_dim == 64) { if (ds == 2) LAUNCH_DA(64, 2); else LAUNCH_DA(64, 1); }
   else return GR_EINVAL;
 #undef LAUNCH_DA
+  GR_CHECK_LAUNCH();
+  return GR_OK;
+}
+
+// Paged form: k_pool [pages, H, 64, hd], vt_pool [pages, H, hd, 64]; row b's key s in page block_table[b * table_ld + s / 64].
+extern "C" int gr_decode_attention_paged(const void* q, const void* k_pool, const void* vt_pool, void* out, const int* kv_len, int B,
+                                         int H, int Smax, const int* block_table, int table_ld, int head_dim, int q_pos0, float scale,
+                                         const int* pos_dev, int pos_stride, int nsplit, float* parts, hipStream_t stream) {
+  if (GR_SP) return GR_EINVAL;
+  if (!q || !k_pool || !vt_pool || !out || !block_table || B <= 0 || H <= 0 || Smax <= 0 || Smax > DEC_SMAX) return GR_EINVAL;
+  if (table_ld <= 0 || table_ld > DEC_SMAX / 64 || Smax > table_ld * 64) return GR_EINVAL;
+  if (nsplit < 1 || nsplit > 16 || (nsplit > 1 && !parts)) return GR_EINVAL;
+  if (!pos_dev && (q_pos0 < 0 || q_pos0 + 1 > Smax)) return GR_EINVAL;
+  const int sc_len = (Smax + 63) & ~63;
+  const size_t lds = (size_t)sc_len * sizeof(float) + (size_t)(sc_len / 64) * sizeof(int);
+  const int ds = B * H * nsplit <= DA_DSPLIT_MAX_BLOCKS ? 2 : 1;
+  // kv_stride carries the row capacity (Smax): the visible length of a row never reaches past its table
+#define LAUNCH_DAP(HDV, DSV)                                                                                                     \
+  hipLaunchKernelGGL((decode_attention_kernel<HDV, DSV, true>), dim3(B * H, nsplit, DSV), dim3(1024), lds, stream,               \
+                     (const bf16_t*)q, (const bf16_t*)k_pool, (const bf16_t*)vt_pool, (bf16_t*)out, kv_len, H, Smax, q_pos0, scale, \
+                     pos_dev, pos_stride, parts, block_table, table_ld, sc_len)
+  if (head_dim == 128) { if (ds == 2) LAUNCH_DAP(128, 2); else LAUNCH_DAP(128, 1); }
+  else if (head_dim == 64) { if (ds == 2) LAUNCH_DAP(64, 2); else LAUNCH_DAP(64, 1); }
+  else return GR_EINVAL;
+#undef LAUNCH_DAP
   GR_CHECK_LAUNCH();
   return GR_OK;
 }

@@ -37,7 +37,8 @@
 typedef __attribute__((ext_vector_type(8))) int g8_i32x8;
 typedef __attribute__((ext_vector_type(4))) int g8_i32x4;
 
-template <int MB>
+// PAGED: epi 3 writes K / V^T into the paged cache (gemv_args.h; gr_gemv_fused_paged)
+template <int MB, bool PAGED = false>
 __global__ __launch_bounds__(256, G8_WG_PER_CU) void gemv_fp8_kernel(GemvFArgs p) {
   constexpr int ROWS = G8_ROWS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -355,7 +356,8 @@ __global__ __launch_bounds__(256, G8_WG_PER_CU) void gemv_fp8_kernel(GemvFArgs p
           const float partner = __shfl_xor(a, 32, 64);  // row rr <-> rr +- 8 = d <-> d +- HD/2: two fg steps = 32 lanes away
           if (ok) {
             if (sect == 2) {
-              p.vt[(bh * p.HD + d) * p.kv_stride + pos] = f2bf(y[r]);
+              if constexpr (PAGED) p.vt[gf_vt_page_off(p, m, hh, pos, d)] = f2bf(y[r]);
+              else p.vt[(bh * p.HD + d) * p.kv_stride + pos] = f2bf(y[r]);
             } else {
               float o = a;
               if (p.cosT) {
@@ -364,6 +366,7 @@ __global__ __launch_bounds__(256, G8_WG_PER_CU) void gemv_fp8_kernel(GemvFArgs p
                 o = a * p.cosT[(long)pos * HALF + dc] + sgn * partner * p.sinT[(long)pos * HALF + dc];
               }
               if (sect == 0) p.q[bh * p.HD + d] = f2bf(o);
+              else if constexpr (PAGED) p.kc[gf_k_page_off(p, m, hh, pos, d)] = f2bf(o);
               else p.kc[(bh * p.kv_stride + pos) * p.HD + d] = f2bf(o);
             }
           }
@@ -384,7 +387,9 @@ int gr_launch_gemv_fp8(const GemvFArgs& p, int MB, int n_cu, hipStream_t stream)
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)gemv_fp8_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemv_fp8_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
+        hipFuncSetAttribute((const void*)gemv_fp8_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
+        hipFuncSetAttribute((const void*)gemv_fp8_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
+        hipFuncSetAttribute((const void*)gemv_fp8_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
       return GR_EINVAL;
     attr_set = true;
   }
@@ -398,7 +403,10 @@ int gr_launch_gemv_fp8(const GemvFArgs& p, int MB, int n_cu, hipStream_t stream)
   const int cap = G8_WG_PER_CU * n_cu, rounds = (groups + cap - 1) / cap;
   const dim3 grid((groups + rounds - 1) / rounds);
 #endif
-  if (MB == 4) hipLaunchKernelGGL(gemv_fp8_kernel<4>, grid, dim3(256), lds, stream, p);
+  if (p.table) {
+    if (MB == 4) hipLaunchKernelGGL((gemv_fp8_kernel<4, true>), grid, dim3(256), lds, stream, p);
+    else hipLaunchKernelGGL((gemv_fp8_kernel<8, true>), grid, dim3(256), lds, stream, p);
+  } else if (MB == 4) hipLaunchKernelGGL(gemv_fp8_kernel<4>, grid, dim3(256), lds, stream, p);
   else hipLaunchKernelGGL(gemv_fp8_kernel<8>, grid, dim3(256), lds, stream, p);
   return GR_OK;
 }

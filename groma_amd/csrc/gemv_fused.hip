@@ -41,7 +41,8 @@
 // paid once per workgroup, not once per group (first version: 2.8 TB/s on the QKV / gate-up / head shapes, because every
 // 8-row group redid it), and the first two slices of the NEXT group are requested before the butterfly / LDS exchange /
 // epilogue of the current one, so the weight stream does not drain between groups.
-template <int MB, bool XG>
+// PAGED (gr_gemv_fused_paged, epi 3 only): the K row / V^T column of a batch row go to its page of the paged cache (gemv_args.h).
+template <int MB, bool XG, bool PAGED = false>
 __global__ __launch_bounds__(256, (XG && MB == 8) ? 1 : 2) void gemv_fused_kernel(GemvFArgs p) {
   constexpr int ROWS = GF_ROWS;  // rows of W per group
   constexpr int NV = ROWS * MB;  // dot products per row group (32 at <= 4 batch rows, 64 at 8): lanes 0..NV-1 own one each after the butterfly
@@ -345,7 +346,8 @@ __global__ __launch_bounds__(256, (XG && MB == 8) ? 1 : 2) void gemv_fused_kerne
           const int pos = p.pos_dev ? p.pos_dev[m * p.pos_stride] : p.pos0;
           const long bh = (long)m * p.H + hh;
           if (sect == 2) {
-            p.vt[(bh * p.HD + d) * p.kv_stride + pos] = f2bf(val);
+            if constexpr (PAGED) p.vt[gf_vt_page_off(p, m, hh, pos, d)] = f2bf(val);
+            else p.vt[(bh * p.HD + d) * p.kv_stride + pos] = f2bf(val);
           } else {
             float o = a;
             if (p.cosT) {
@@ -354,6 +356,7 @@ __global__ __launch_bounds__(256, (XG && MB == 8) ? 1 : 2) void gemv_fused_kerne
               o = a * p.cosT[(long)pos * HALF + dc] + sgn * partner * p.sinT[(long)pos * HALF + dc];
             }
             if (sect == 0) p.q[bh * p.HD + d] = f2bf(o);
+            else if constexpr (PAGED) p.kc[gf_k_page_off(p, m, hh, pos, d)] = f2bf(o);
             else p.kc[(bh * p.kv_stride + pos) * p.HD + d] = f2bf(o);
           }
         }
@@ -370,7 +373,8 @@ __global__ __launch_bounds__(256, (XG && MB == 8) ? 1 : 2) void gemv_fused_kerne
 int gr_prof_begin(hipStream_t stream, int M, int N, int K, int tag);
 void gr_prof_end(hipStream_t stream, int idx);
 
-extern "C" int gr_gemv_fused(const gr_gemv_desc* d, hipStream_t stream) {
+// table != null: gr_gemv_fused_paged (epi 3 into the paged cache); kv_stride is then the row capacity table_ld * 64
+static int gemv_fused_launch(const gr_gemv_desc* d, const int* table, int table_ld, hipStream_t stream) {
   if (GR_SP) return GR_EINVAL;  // no split-operand form: a decode step of the reference-precision build runs the general kernels
   if (!d || !d->W || d->M <= 0 || d->M > 8 || d->N <= 0 || d->K <= 0 || d->K % 64 != 0 || d->ldw < d->K) return GR_EINVAL;
   if (d->x_mode < 0 || d->x_mode > 2 || d->epi < 0 || d->epi > 3) return GR_EINVAL;
@@ -399,10 +403,13 @@ extern "C" int gr_gemv_fused(const gr_gemv_desc* d, hipStream_t stream) {
   p.q = (bf16_t*)d->q; p.kc = (bf16_t*)d->kc; p.vt = (bf16_t*)d->vt; p.cosT = d->cosT; p.sinT = d->sinT;
   p.H = d->H; p.HD = d->HD; p.pos0 = d->pos0; p.kv_stride = d->kv_stride; p.pos_dev = d->pos_dev; p.pos_stride = d->pos_stride;
   p.w_scale = d->w_scale;
+  p.table = table; p.table_ld = table_ld;
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)gemv_fused_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemv_fused_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
+        hipFuncSetAttribute((const void*)gemv_fused_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
+        hipFuncSetAttribute((const void*)gemv_fused_kernel<4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
+        hipFuncSetAttribute((const void*)gemv_fused_kernel<8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
       return GR_EINVAL;
     attr_set = true;
   }
@@ -427,7 +434,15 @@ extern "C" int gr_gemv_fused(const gr_gemv_desc* d, hipStream_t stream) {
     return GR_OK;
   }
   const int prof = gr_prof_begin(stream, d->M, d->N, d->K, 8 | 32);
-  if (d->x_mode == 0) {
+  if (table) {
+    if (d->x_mode == 0) {
+      if (MB == 4) hipLaunchKernelGGL((gemv_fused_kernel<4, true, true>), grid, dim3(256), 0, stream, p);
+      else hipLaunchKernelGGL((gemv_fused_kernel<8, true, true>), grid, dim3(256), 0, stream, p);
+    } else {
+      if (MB == 4) hipLaunchKernelGGL((gemv_fused_kernel<4, false, true>), grid, dim3(256), lds, stream, p);
+      else hipLaunchKernelGGL((gemv_fused_kernel<8, false, true>), grid, dim3(256), lds, stream, p);
+    }
+  } else if (d->x_mode == 0) {
     if (MB == 4) hipLaunchKernelGGL((gemv_fused_kernel<4, true>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((gemv_fused_kernel<8, true>), grid, dim3(256), 0, stream, p);
   } else {
@@ -437,4 +452,16 @@ extern "C" int gr_gemv_fused(const gr_gemv_desc* d, hipStream_t stream) {
   gr_prof_end(stream, prof);
   GR_CHECK_LAUNCH();
   return GR_OK;
+}
+
+extern "C" int gr_gemv_fused(const gr_gemv_desc* d, hipStream_t stream) { return gemv_fused_launch(d, nullptr, 0, stream); }
+
+// The QKV stream (epi 3) writing K and V^T into a paged cache: d->kc [pages, H, 64, HD], d->vt [pages, H, HD, 64]; row m's position pos
+// lands in page block_table[m * table_ld + pos / 64] (table_ld <= 128).  d->kv_stride is ignored (the row capacity is table_ld * 64).
+extern "C" int gr_gemv_fused_paged(const gr_gemv_desc* d, const int* block_table, int table_ld, hipStream_t stream) {
+  if (GR_SP) return GR_EINVAL;
+  if (!d || !block_table || d->epi != 3 || table_ld <= 0 || table_ld > 128) return GR_EINVAL;
+  gr_gemv_desc e = *d;
+  e.kv_stride = table_ld * 64;
+  return gemv_fused_launch(&e, block_table, table_ld, stream);
 }

@@ -85,17 +85,24 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
   }
 }
 #else
-template <int HD>
+// PAGED (gr_qkv_split_paged, L = 1): k is a pool [pages, H, 64, HD], vt a pool [pages, H, HD, 64]; row b's position pos is in page
+// table[b * table_ld + pos / 64] (page 0, the sink page, past the end of the table).  The values are the slot form's, bit for bit.
+template <int HD, bool PAGED = false>
 __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ q,
                                                         bf16_t* __restrict__ k, bf16_t* __restrict__ vt,
                                                         const float* __restrict__ cosT, const float* __restrict__ sinT,
                                                         int B, int H, int L, int pos0_arg, int kv_stride,
-                                                        const int* __restrict__ pos_dev, int pos_stride) {
+                                                        const int* __restrict__ pos_dev, int pos_stride,
+                                                        const int* __restrict__ table, int table_ld) {
   __shared__ __attribute__((aligned(16))) bf16_t vs[64][HD + 8];
   const int t0 = blockIdx.x * 64;
   const int h = blockIdx.y, b = blockIdx.z;
   // device-resident write position (graph-captured / ragged decode): row b appends at pos_dev[b * pos_stride]
   const int pos0 = pos_dev ? pos_dev[b * pos_stride] : pos0_arg;
+  auto page = [&](int pos) -> long {
+    const int i = pos >> 6;
+    return (unsigned)i < (unsigned)table_ld ? (long)table[(long)b * table_ld + i] : 0L;
+  };
   const int tid = threadIdx.x;
   const long row_stride = 3L * H * HD;
   constexpr int HALF = HD / 2;
@@ -115,7 +122,9 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
     for (int which = 0; which < 2; ++which) {
       const bf16_t* sp = src + (long)which * H * HD;
       if (which == 0 && !q) continue;  // q stays in the fused buffer: gr_attention_bf16 reads (and rotates) it there
-      bf16_t* dst = which == 0 ? q + (((long)b * H + h) * L + t) * HD : k + (((long)b * H + h) * kv_stride + pos) * HD;
+      bf16_t* dst;
+      if constexpr (PAGED) dst = which == 0 ? q + (((long)b * H + h) * L + t) * HD : k + ((page(pos) * H + h) * 64 + (pos & 63)) * HD;
+      else dst = which == 0 ? q + (((long)b * H + h) * L + t) * HD : k + (((long)b * H + h) * kv_stride + pos) * HD;
       const bf16x8 x = *(const bf16x8*)(sp + d);
       if (cosT) {
         const int dp = d < HALF ? d + HALF : d - HALF;  // rotate_half partner
@@ -146,7 +155,9 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
     const int d = it >> 3, seg = it & 7;
     const int tb = t0 + seg * 8;
     if (tb >= L) continue;
-    bf16_t* dst = vt + (((long)b * H + h) * HD + d) * kv_stride + pos0 + tb;
+    bf16_t* dst;  // (PAGED: L = 1, so the one column written lies in pos0's page)
+    if constexpr (PAGED) dst = vt + ((page(pos0 + tb) * H + h) * HD + d) * 64 + ((pos0 + tb) & 63);
+    else dst = vt + (((long)b * H + h) * HD + d) * kv_stride + pos0 + tb;
     if (aligned && tb + 8 <= L) {
       union { bf16x8 v; bf16_t e[8]; } o;
 #pragma unroll
@@ -169,12 +180,86 @@ extern "C" int gr_qkv_split(const void* qkv, void* q, void* k, void* vt, const f
   if ((cosT == nullptr) != (sinT == nullptr)) return GR_EINVAL;
   if (GR_SP && kv_stride % 32 != 0) return GR_EINVAL;
   dim3 grid(gr_cdiv(L, 64), H, B);
+#if GR_SP
+#define QKV_TAIL
+#else
+#define QKV_TAIL , nullptr, 0
+#endif
   if (head_dim == 128)
     hipLaunchKernelGGL(qkv_split_kernel<128>, grid, dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k,
-                       (bf16_t*)vt, cosT, sinT, B, H, L, pos0, kv_stride, pos_dev, pos_stride);
+                       (bf16_t*)vt, cosT, sinT, B, H, L, pos0, kv_stride, pos_dev, pos_stride QKV_TAIL);
   else if (head_dim == 64)
     hipLaunchKernelGGL(qkv_split_kernel<64>, grid, dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k,
-                       (bf16_t*)vt, cosT, sinT, B, H, L, pos0, kv_stride, pos_dev, pos_stride);
+                       (bf16_t*)vt, cosT, sinT, B, H, L, pos0, kv_stride, pos_dev, pos_stride QKV_TAIL);
+  else return GR_EINVAL;
+#undef QKV_TAIL
+  GR_CHECK_LAUNCH();
+  return GR_OK;
+}
+
+// The decode step's RoPE + K / V^T write (L = 1) into a paged cache: k_pool [pages, H, 64, hd], vt_pool [pages, H, hd, 64], row b's
+// position in page block_table[b * table_ld + pos / 64].  No split-operand form.
+extern "C" int gr_qkv_split_paged(const void* qkv, void* q, void* k_pool, void* vt_pool, const float* cosT, const float* sinT, int B,
+                                  int H, int L, int head_dim, int pos0, const int* block_table, int table_ld, const int* pos_dev,
+                                  int pos_stride, hipStream_t stream) {
+  if (GR_SP) return GR_EINVAL;
+  if (!qkv || !k_pool || !vt_pool || !block_table || B <= 0 || H <= 0 || L != 1) return GR_EINVAL;
+  if ((cosT == nullptr) != (sinT == nullptr) || table_ld <= 0 || table_ld > 128) return GR_EINVAL;
+  if (!pos_dev && (pos0 < 0 || pos0 >= table_ld * 64)) return GR_EINVAL;
+#if !GR_SP
+  dim3 grid(1, H, B);
+  if (head_dim == 128)
+    hipLaunchKernelGGL((qkv_split_kernel<128, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k_pool,
+                       (bf16_t*)vt_pool, cosT, sinT, B, H, 1, pos0, 64, pos_dev, pos_stride, block_table, table_ld);
+  else if (head_dim == 64)
+    hipLaunchKernelGGL((qkv_split_kernel<64, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k_pool,
+                       (bf16_t*)vt_pool, cosT, sinT, B, H, 1, pos0, 64, pos_dev, pos_stride, block_table, table_ld);
+  else return GR_EINVAL;
+  GR_CHECK_LAUNCH();
+#endif
+  return GR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Staged prefill rows -> their pages (the continuous batcher's admission into a paged cache).  k_src [n_src, H, S, hd] and
+// vt_src [n_src, H, hd, S] are the staging cache; entry i moves staging row src_rows[i] into the pages of table row dst_rows[i]
+// (< n_dst): every whole 64-position page below lens[i] (clamped to max_len).  One block per (page, head, entry); 16-B copies
+// (a K page of a head is one contiguous 64 x hd run on both sides, a V^T page hd runs of 64).
+template <int HD>
+__global__ __launch_bounds__(256) void kv_scatter_pages_kernel(const bf16_t* __restrict__ ks, const bf16_t* __restrict__ vs,
+                                                               bf16_t* __restrict__ kp, bf16_t* __restrict__ vp,
+                                                               const int* __restrict__ table, int table_ld,
+                                                               const int* __restrict__ src_rows, const int* __restrict__ dst_rows,
+                                                               const int* __restrict__ lens, int n_src, int n_dst, int H, int S,
+                                                               int max_len) {
+  const int j = blockIdx.x, h = blockIdx.y, i = blockIdx.z;
+  const int sr = src_rows[i], dr = dst_rows[i];
+  const int len = min(lens[i], max_len);
+  if (sr < 0 || sr >= n_src || dr < 0 || dr >= n_dst || j * 64 >= len) return;
+  const long pg = table[(long)dr * table_ld + j];
+  const bf16x8* ksrc = (const bf16x8*)(ks + (((long)sr * H + h) * S + j * 64) * HD);
+  bf16x8* kdst = (bf16x8*)(kp + (pg * H + h) * 64 * HD);
+  for (int c = threadIdx.x; c < 64 * HD / 8; c += 256) kdst[c] = ksrc[c];
+  for (int c = threadIdx.x; c < HD * 8; c += 256) {
+    const int d = c >> 3, e = c & 7;
+    *(bf16x8*)(vp + ((pg * H + h) * HD + d) * 64 + e * 8) = *(const bf16x8*)(vs + (((long)sr * H + h) * HD + d) * S + j * 64 + e * 8);
+  }
+}
+
+extern "C" int gr_kv_scatter_pages(const void* k_src, const void* vt_src, void* k_pool, void* vt_pool, const int* block_table,
+                                   int table_ld, const int* src_rows, const int* dst_rows, const int* lens, int n, int n_src,
+                                   int n_dst, int H, int S, int head_dim, int max_len, hipStream_t stream) {
+  if (GR_SP) return GR_EINVAL;
+  if (!k_src || !vt_src || !k_pool || !vt_pool || !block_table || !src_rows || !dst_rows || !lens) return GR_EINVAL;
+  if (n <= 0 || n_src <= 0 || n_dst <= 0 || H <= 0 || S <= 0 || S % 64 != 0 || table_ld <= 0 || table_ld > 128) return GR_EINVAL;
+  if (max_len <= 0 || max_len > S || max_len > table_ld * 64) return GR_EINVAL;
+  dim3 grid(gr_cdiv(max_len, 64), H, n);
+  if (head_dim == 128)
+    hipLaunchKernelGGL(kv_scatter_pages_kernel<128>, grid, dim3(256), 0, stream, (const bf16_t*)k_src, (const bf16_t*)vt_src,
+                       (bf16_t*)k_pool, (bf16_t*)vt_pool, block_table, table_ld, src_rows, dst_rows, lens, n_src, n_dst, H, S, max_len);
+  else if (head_dim == 64)
+    hipLaunchKernelGGL(kv_scatter_pages_kernel<64>, grid, dim3(256), 0, stream, (const bf16_t*)k_src, (const bf16_t*)vt_src,
+                       (bf16_t*)k_pool, (bf16_t*)vt_pool, block_table, table_ld, src_rows, dst_rows, lens, n_src, n_dst, H, S, max_len);
   else return GR_EINVAL;
   GR_CHECK_LAUNCH();
   return GR_OK;

@@ -632,6 +632,34 @@ class KVCache:
         self.smax, self._addr = smax, None
 
 
+class PagedKVCache:
+    """Paged device KV cache (the continuous batcher's kv_pages mode): per layer a K pool [pages + 1, H, 64, hd] and a V^T pool
+    [pages + 1, H, hd, 64], and ONE block table int32 [rows, max_len / 64] shared by all layers -- row b's position s lives in page
+    table[b, s // 64] of every layer's pools.  Page 0 is the sink page: never handed to a request, every unowned table entry points
+    at it, so what masked rows write lands there.  Neither the pools nor the table ever move (a captured decode step stays valid);
+    the table's contents change in place.  Only the decode step (L = 1, weight-streaming kernels) reads or writes it."""
+    paged = True
+    PAGE = 64
+
+    def __init__(self, n_layers, rows, H, hd, smax, n_pages, device):
+        if smax % 64 or smax // 64 > 128:
+            raise ValueError("a paged cache holds at most 128 pages (8192 positions) per row, in multiples of 64")
+        self.k = [torch.zeros((n_pages + 1, H, 64, hd), dtype=H16(), device=device) for _ in range(n_layers)]
+        self.vt = [torch.zeros((n_pages + 1, H, hd, 64), dtype=H16(), device=device) for _ in range(n_layers)]
+        self.table = torch.zeros((rows, smax // 64), dtype=I32, device=device)
+        self.seq_len, self.smax, self.bs, self.n_pages, self.sp = 0, smax, rows, n_pages, 1
+        self._addr = None
+
+    def __len__(self):
+        return len(self.k)
+
+    def __bool__(self):
+        return True
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.k + self.vt) + self.table.numel() * 4
+
+
 def cache_addresses(cache):
     """every layer's K / V^T address (+ capacity) of a KVCache-like object (KVCache, serving's row view): part of the key of a
     captured prefill graph.  Memoised on the object; KVCache.grow() drops the memo."""
@@ -666,6 +694,29 @@ class LlamaEngine:
         with self._st("attn"):   # K / V^T are the attention stage's operands
             return KVCache(len(self.w["layers"]), bs, self.H, self.hd, _ru(smax, 64), device)
 
+    def new_paged_cache(self, rows, smax, n_pages, device):
+        """PagedKVCache of n_pages usable pages (+ the sink page) for `rows` rows of up to smax positions"""
+        if self.prec is not None or ops.SP() != 1:
+            raise ValueError("a paged KV cache needs a single-type 16-bit or e4m3 stack (its decode step runs on the weight streams)")
+        return PagedKVCache(len(self.w["layers"]), rows, self.H, self.hd, smax, n_pages, device)
+
+    def decode_path(self, M, smax, L=1, states=None):
+        """which kernels a step of M rows x L positions over a cache of smax positions runs on: "fused" (the <= 8-row weight streams,
+        csrc/gemv_fused.hip / gemv_fp8.hip), "wide" (9..64 rows, csrc/gemm_skinny.hip) or None (the general kernels)"""
+        w, T = self.w, self.T
+        # (e4m3 weights, round 5: the streams read the e4m3 bytes on the matrix unit -- csrc/gemv_fp8.hip, half the HBM traffic per
+        #  token; the quantised operand is staged as M x K bytes in LDS, plus the merged context as 16-bit values in the o-proj)
+        fits8 = not w["fp8"] or (_ru(M, 4) * (max(T, self.I) + 16) <= 128 * 1024 and _ru(M, 4) * (3 * T + 16) <= 128 * 1024 and T <= 4096
+                                 and max(T, self.I) <= 12288 and T % 128 == 0 and self.I % 128 == 0 and self.Vpad % 16 == 0
+                                 and self.hd % 32 == 0)   # (the e4m3 QKV stream rotates heads in 32-dim halves)
+        if FUSED_DECODE and L == 1 and M <= 8 and fits8 and T <= 8192 and smax <= 8192 and ops.SP() == 1 and states is None \
+                and self.prec is None:
+            return "fused"
+        if WIDE_DECODE and L == 1 and 8 < M <= 64 and ops.SP() == 1 and self.prec is None and states is None \
+                and T % 32 == 0 and self.I % 32 == 0 and smax <= 8192 and (not w["fp8"] or (T % 128 == 0 and self.I % 128 == 0)):
+            return "wide"
+        return None
+
     def forward(self, h, bs, L, cache, kv_len=None, all_logits=True, pos_dev=None, pos_stride=0, states=None):
         """h: f32 [bs*L, T] input embeddings (consumed as the residual stream, updated in place).
         states: a list that receives a copy of the residual stream in front of every layer (HF `all_hidden_states`, R:
@@ -678,18 +729,16 @@ class LlamaEngine:
         M = bs * L
         dyn = pos_dev is not None
         past = 0 if dyn else cache.seq_len
+        path = self.decode_path(M, cache.smax, L, states)
+        if getattr(cache, "paged", False) and (path is None or not dyn or bs > cache.bs):
+            # the general kernels (and every L > 1 path) address a slot arena: never hand them the pools of a paged cache
+            raise ValueError("a paged KV cache is read and written only by the decode step of the weight-streaming kernels "
+                             "(L = 1, <= 64 rows, device-resident positions, a single-type 16-bit or e4m3 stack)")
         if not dyn and past + L > cache.smax:
             cache.grow(_ru(past + L + 64, 64))
-        # (e4m3 weights, round 5: the streams read the e4m3 bytes on the matrix unit -- csrc/gemv_fp8.hip, half the HBM traffic per
-        #  token; the quantised operand is staged as M x K bytes in LDS, plus the merged context as 16-bit values in the o-proj)
-        fits8 = not w["fp8"] or (_ru(bs, 4) * (max(T, self.I) + 16) <= 128 * 1024 and _ru(bs, 4) * (3 * T + 16) <= 128 * 1024 and T <= 4096
-                                 and max(T, self.I) <= 12288 and T % 128 == 0 and self.I % 128 == 0 and self.Vpad % 16 == 0
-                                 and self.hd % 32 == 0)   # (the e4m3 QKV stream rotates heads in 32-dim halves)
-        if FUSED_DECODE and L == 1 and M <= 8 and fits8 and T <= 8192 and cache.smax <= 8192 and ops.SP() == 1 and states is None \
-                and self.prec is None:
+        if path == "fused":
             return self._decode_forward(h, bs, cache, kv_len, pos_dev, pos_stride, past)
-        if WIDE_DECODE and L == 1 and 8 < M <= 64 and ops.SP() == 1 and self.prec is None and states is None \
-                and T % 32 == 0 and self.I % 32 == 0 and cache.smax <= 8192 and (not w["fp8"] or (T % 128 == 0 and self.I % 128 == 0)):
+        if path == "wide":
             return self._decode_forward_wide(h, bs, cache, kv_len, pos_dev, pos_stride, past)
         # A decode step that does not fit the weight-streaming paths (more than 64 rows, pair operands, e4m3 beyond 8 rows, > 8192 keys)
         # runs the general kernels below.  Its scratch may be baked into GreedyDecoder's captured hipGraph, so -- like _decode_forward --
@@ -827,6 +876,7 @@ class LlamaEngine:
         kernels of their own here (a 64-row operand no longer fits a workgroup's prologue).  Never-moved buffers: the step is captured."""
         w, ws, T, H, hd = self.w, self.ws, self.T, self.H, self.hd
         dyn = pos_dev is not None
+        paged = getattr(cache, "paged", False)   # (PagedKVCache: pages looked up through cache.table)
         fp8 = w["fp8"]
         x = ws.get("decw_x", (bs, T), H16(), exact=True)
         qkv = ws.get("decw_qkv", (bs, 3 * T), H16(), exact=True)
@@ -852,10 +902,16 @@ class LlamaEngine:
 
         for i, Lw in enumerate(w["layers"]):
             lin(h, Lw["n1"], Lw["wqkv"], out=qkv)
-            ops.qkv_split(qkv, q, cache.k[i], cache.vt[i], B=bs, H=H, L=1, hd=hd, pos0=past, cos=w["cos"], sin=w["sin"],
-                          pos_dev=pos_dev, pos_stride=pos_stride)
-            ops.decode_attention(q, cache.k[i], cache.vt[i], ctx, Smax=cache.smax if dyn else past + 1, q_pos0=past, kv_len=kv_len,
-                                 pos_dev=pos_dev, pos_stride=pos_stride, nsplit=1)
+            if paged:
+                ops.qkv_split_paged(qkv, q, cache.k[i], cache.vt[i], cache.table, B=bs, H=H, hd=hd, cos=w["cos"], sin=w["sin"],
+                                    pos_dev=pos_dev, pos_stride=pos_stride)
+                ops.decode_attention_paged(q, cache.k[i], cache.vt[i], ctx, cache.table, Smax=cache.smax, kv_len=kv_len,
+                                           pos_dev=pos_dev, pos_stride=pos_stride, nsplit=1)
+            else:
+                ops.qkv_split(qkv, q, cache.k[i], cache.vt[i], B=bs, H=H, L=1, hd=hd, pos0=past, cos=w["cos"], sin=w["sin"],
+                              pos_dev=pos_dev, pos_stride=pos_stride)
+                ops.decode_attention(q, cache.k[i], cache.vt[i], ctx, Smax=cache.smax if dyn else past + 1, q_pos0=past,
+                                     kv_len=kv_len, pos_dev=pos_dev, pos_stride=pos_stride, nsplit=1)
             lin16(ctx, Lw["wo"], resid=h, out=h, out_f32=True)
             lin(h, Lw["n2"], Lw["wgu"], act=3, out=y)
             lin16(y, Lw["wd"], resid=h, out=h, out_f32=True)
@@ -875,6 +931,7 @@ class LlamaEngine:
         epilogue is its consumer (RoPE + cache write, in-place residual update, SwiGLU): csrc/gemv_fused.hip."""
         w, ws, T, H, hd = self.w, self.ws, self.T, self.H, self.hd
         dyn = pos_dev is not None
+        paged = getattr(cache, "paged", False)   # (PagedKVCache: pages looked up through cache.table)
         q = ws.get("dec_q", h16(bs, H, 1, hd), H16(), exact=True)
         ctx = ws.get("dec_ctx", h16(bs, T), H16(), exact=True)
         y = ws.get("dec_y", h16(bs, self.I), H16(), exact=True)
@@ -885,9 +942,13 @@ class LlamaEngine:
                 _trace("dec0.h_in", h)
             ops.gemv_fused(Lw["wqkv"][0], M=bs, norm=(h, Lw["n1"], self.eps), **ws8(Lw["wqkv"]),
                            qkv=dict(q=q, k=cache.k[i], vt=cache.vt[i], cos=w["cos"], sin=w["sin"], H=H, hd=hd, pos0=past,
-                                    pos_dev=pos_dev, pos_stride=pos_stride))
-            att = ops.decode_attention(q, cache.k[i], cache.vt[i], ctx, Smax=cache.smax if dyn else past + 1, q_pos0=past,
-                                       kv_len=kv_len, pos_dev=pos_dev, pos_stride=pos_stride)
+                                    pos_dev=pos_dev, pos_stride=pos_stride, **(dict(table=cache.table) if paged else {})))
+            if paged:
+                att = ops.decode_attention_paged(q, cache.k[i], cache.vt[i], ctx, cache.table, Smax=cache.smax, kv_len=kv_len,
+                                                 pos_dev=pos_dev, pos_stride=pos_stride)
+            else:
+                att = ops.decode_attention(q, cache.k[i], cache.vt[i], ctx, Smax=cache.smax if dyn else past + 1, q_pos0=past,
+                                           kv_len=kv_len, pos_dev=pos_dev, pos_stride=pos_stride)
             if t0:
                 _trace("dec0.q", q)
                 TRACE["dec0.nsplit"] = att[1] if isinstance(att, tuple) else 1

@@ -339,7 +339,9 @@ def gemv_fused(w, *, M, x=None, norm=None, a_parts=None, out=None, resid=None, s
     Operand (exactly one): x = 16-bit [M,K]; norm = (h f32 [M,K], gamma, eps) -> RMSNorm in the prologue; a_parts = the
     un-merged output of decode_attention(nsplit > 1).
     Result (exactly one): out f32 [M,N]; resid f32 [M,N] (+= y in place); swiglu_out 16-bit [M, N/2] (interleaved gate / up rows);
-    qkv = dict(q, k, vt, cos, sin, H, hd, pos0, pos_dev, pos_stride): RoPE + q / K-cache row / V^T-cache column."""
+    qkv = dict(q, k, vt, cos, sin, H, hd, pos0, pos_dev, pos_stride): RoPE + q / K-cache row / V^T-cache column; with table= (int32
+    [rows, max_len / 64]) k / vt are the pools of a paged cache (engine.PagedKVCache) and the row's page is looked up
+    (gr_gemv_fused_paged)."""
     lib = _lib.load()
     if w.dtype == FP8:   # e4m3 weight stream (w_scale = the per-row scale): half the bytes per token, operand quantised in the prologue
         if w_scale is None:
@@ -383,6 +385,11 @@ def gemv_fused(w, *, M, x=None, norm=None, a_parts=None, out=None, resid=None, s
         if pd is not None:
             _chk(pd, I32, "pos_dev")
             d.pos_dev, d.pos_stride = pd.data_ptr(), qkv.get("pos_stride", 0)
+        table = qkv.get("table")
+        if table is not None:
+            _chk(table, I32, "table")
+            _lib.check(lib.gr_gemv_fused_paged(ctypes.byref(d), _p(table), table.shape[1], _stream()), "gr_gemv_fused_paged")
+            return
     _lib.check(lib.gr_gemv_fused(ctypes.byref(d), _stream()), "gr_gemv_fused")
 
 
@@ -393,6 +400,18 @@ def decode_attention(q, k, vt, out, *, Smax, q_pos0=0, kv_len=None, scale=None, 
     """q [B,H,1,hd] against the cache k [B,H,kv_stride,hd] / vt [B,H,hd,kv_stride] -> out bf16 [B, H*hd].
     nsplit None = enough key slices per (row, head) to put a block on every CU.  With nsplit > 1 `out` is NOT written:
     the return value is (parts, nsplit, hd, B) for gemv_partials(..., a_parts=...) (the o-proj merges the slices)."""
+    return _decode_attention(q, k, vt, out, None, Smax, q_pos0, kv_len, scale, pos_dev, pos_stride, nsplit)
+
+
+def decode_attention_paged(q, k_pool, vt_pool, out, table, *, Smax, q_pos0=0, kv_len=None, scale=None, pos_dev=None, pos_stride=0,
+                           nsplit=None):
+    """decode_attention over a paged cache: k_pool [pages, H, 64, hd], vt_pool [pages, H, hd, 64], table int32 [>= B, Smax / 64]
+    (row b's key s in page table[b, s // 64]).  Same result (the same bits) and return convention as decode_attention."""
+    _chk(table, I32, "table")
+    return _decode_attention(q, k_pool, vt_pool, out, table, Smax, q_pos0, kv_len, scale, pos_dev, pos_stride, nsplit)
+
+
+def _decode_attention(q, k, vt, out, table, Smax, q_pos0, kv_len, scale, pos_dev, pos_stride, nsplit):
     lib = _lib.load()
     _chk(q, H16(), "q"); _chk(k, H16(), "k"); _chk(vt, H16(), "vt"); _chk(out, H16(), "out")
     B, H, _, hd = q.shape
@@ -413,9 +432,16 @@ def decode_attention(q, k, vt, out, *, Smax, q_pos0=0, kv_len=None, scale=None, 
         if key not in _DEC_ATT_WS:
             _DEC_ATT_WS[key] = torch.empty((B * H * nsplit * (hd + 2),), dtype=F32, device=q.device)
         parts = _DEC_ATT_WS[key]
-    _lib.check(lib.gr_decode_attention(_p(q), _p(k), _p(vt), _p(out), _p(kv_len), B, H, Smax, k.shape[2], hd, q_pos0,
-                                       scale, _p(pos_dev), pos_stride, nsplit, _p(parts), _stream()),
-               "gr_decode_attention")
+    if table is None:
+        _lib.check(lib.gr_decode_attention(_p(q), _p(k), _p(vt), _p(out), _p(kv_len), B, H, Smax, k.shape[2], hd, q_pos0,
+                                           scale, _p(pos_dev), pos_stride, nsplit, _p(parts), _stream()),
+                   "gr_decode_attention")
+    else:
+        if table.shape[0] < B:
+            raise ValueError("table has fewer rows than q")
+        _lib.check(lib.gr_decode_attention_paged(_p(q), _p(k), _p(vt), _p(out), _p(kv_len), B, H, Smax, _p(table), table.shape[1],
+                                                 hd, q_pos0, scale, _p(pos_dev), pos_stride, nsplit, _p(parts), _stream()),
+                   "gr_decode_attention_paged")
     if nsplit > 1:
         return parts, nsplit, hd, B
     return out
@@ -499,6 +525,31 @@ def qkv_split(qkv, q, k, vt, *, B, H, L, hd, pos0=0, cos=None, sin=None, pos_dev
         _chk(pos_dev, I32, "pos_dev")
     _lib.check(lib.gr_qkv_split(_p(qkv), _p(q), _p(k), _p(vt), _p(cos), _p(sin), B, H, L, hd, pos0, k.shape[2],
                                 _p(pos_dev), pos_stride, _stream()), "gr_qkv_split")
+
+
+def qkv_split_paged(qkv, q, k_pool, vt_pool, table, *, B, H, hd, pos0=0, cos=None, sin=None, pos_dev=None, pos_stride=0):
+    """qkv_split for one new position per row (L = 1) into a paged cache (pools and table as for decode_attention_paged)"""
+    lib = _lib.load()
+    _chk(qkv, H16(), "qkv"); _chk(k_pool, H16(), "k_pool"); _chk(vt_pool, H16(), "vt_pool"); _chk(table, I32, "table")
+    if table.shape[0] < B:
+        raise ValueError("table has fewer rows than the batch")
+    if pos_dev is not None:
+        _chk(pos_dev, I32, "pos_dev")
+    _lib.check(lib.gr_qkv_split_paged(_p(qkv), _p(q), _p(k_pool), _p(vt_pool), _p(cos), _p(sin), B, H, 1, hd, pos0, _p(table),
+                                      table.shape[1], _p(pos_dev), pos_stride, _stream()), "gr_qkv_split_paged")
+
+
+def kv_scatter_pages(k_src, vt_src, k_pool, vt_pool, table, rows, max_len):
+    """staging cache (k_src [n_src, H, S, hd], vt_src [n_src, H, hd, S]) -> pages: rows = int32 device tensor [3, n] of
+    (staging row, table row, length); every whole 64-position page below min(length, max_len) is copied.  One layer per call."""
+    lib = _lib.load()
+    _chk(k_src, H16(), "k_src"); _chk(vt_src, H16(), "vt_src"); _chk(k_pool, H16(), "k_pool"); _chk(vt_pool, H16(), "vt_pool")
+    _chk(table, I32, "table"); _chk(rows, I32, "rows")
+    n_src, H, S, hd = k_src.shape
+    n = rows.shape[1]
+    _lib.check(lib.gr_kv_scatter_pages(_p(k_src), _p(vt_src), _p(k_pool), _p(vt_pool), _p(table), table.shape[1], _p(rows[0]),
+                                       _p(rows[1]), _p(rows[2]), n, n_src, table.shape[0], H, S, hd, max_len, _stream()),
+               "gr_kv_scatter_pages")
 
 
 def patchify(images, P, Kpad, out=None):

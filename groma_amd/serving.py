@@ -25,6 +25,11 @@ a step -- so the MI355X design batches the decode steps of *different requests*:
 
 Ragged lengths are exact here: each row attends to its own [0, pos] -- the padded-prefix artefact of batched HF
 generate cannot occur because rows are never padded against each other.
+
+With `kv_pages=N` the arena is PAGED instead (engine.PagedKVCache): N pages of 64 positions per layer plus a sink page, and a
+block table that maps each row's positions to pages.  A request reserves the pages of its context bound at admission, keeps those
+its prompt and new tokens can reach, and gives them back when it finishes, so a fixed budget holds more and longer rows than
+`max_rows` slots of `max_len` each.  Admission is FIFO and waits while the head request's pages are not free.
 """
 import threading
 from collections import deque
@@ -67,6 +72,41 @@ class SlotTable:
         return [s for s in range(self.n) if self.owner[s] is not None]
 
 
+class PagePool:
+    """Page bookkeeping of a paged KV cache (host side, no device work): pages 1..n are handed out, page 0 -- the sink page every
+    unowned block-table entry points at -- never is."""
+
+    def __init__(self, n):
+        if n < 1:
+            raise ValueError("a page pool needs at least one page")
+        self.n = n
+        self._free = deque(range(1, n + 1))
+        self._used = set()
+        self.high_water = 0
+
+    def reserve(self, k):
+        """k page ids, or None (nothing taken) when fewer than k are free"""
+        if k < 0:
+            raise ValueError("negative page count")
+        if k > len(self._free):
+            return None
+        ids = [self._free.popleft() for _ in range(k)]
+        self._used.update(ids)
+        self.high_water = max(self.high_water, len(self._used))
+        return ids
+
+    def release(self, ids):
+        ids = list(ids)
+        if len(set(ids)) != len(ids) or any(i not in self._used for i in ids):
+            raise ValueError(f"pages {ids} are not all in use")
+        self._used.difference_update(ids)
+        self._free.extend(ids)
+
+    @property
+    def n_free(self):
+        return len(self._free)
+
+
 @dataclass
 class Request:
     rid: int
@@ -85,6 +125,7 @@ class Request:
     prompt_len: int = 0                     # expanded length L in the cache
     done: bool = False
     error: Optional[str] = None
+    pages: Optional[List[int]] = None       # paged mode: the pages reserved for this request (released when it finishes)
 
 
 class _RowView:
@@ -113,7 +154,11 @@ class _RowView:
 
 class ContinuousBatcher:
     @engine.model_entry(lambda self, *a, **kw: (a[0] if a else kw["model"]).precision)
-    def __init__(self, model, max_rows=8, max_len=1024, use_graph=True, grow_to=None, overlap_admission=None, admit_min=2, admit_hold=8):
+    def __init__(self, model, max_rows=8, max_len=1024, use_graph=True, grow_to=None, overlap_admission=None, admit_min=2, admit_hold=8,
+                 kv_pages=None, admit_rows=None, max_prompt_len=None):
+        """kv_pages=N: a paged KV cache of N pages of 64 positions (engine.PagedKVCache) instead of max_rows slots of max_len positions;
+        max_len is then the per-request cap.  admit_rows (default min(max_rows, 8)) bounds an admission wave, max_prompt_len (default
+        min(max_len, 1024)) the prompt part of a request: the staging cache the prefills land in holds admit_rows x max_prompt_len."""
         if max_rows < 1 or max_rows > 64:
             raise ValueError("max_rows must be in 1..64 (1..8: the fused 8-row weight streams; 9..64: the matrix-unit weight streams, "
                              "csrc/gemm_skinny.hip / gemm_skinny_fp8.hip -- single-type 16-bit or e4m3 models; others fall back to the general kernels)")
@@ -121,12 +166,26 @@ class ContinuousBatcher:
             raise ValueError("max_len must be a multiple of 64 and <= 8192")
         if grow_to is not None and (grow_to % 64 or grow_to < max_len or grow_to > 8192):
             raise ValueError("grow_to must be a multiple of 64 in max_len..8192")
+        self.paged = kv_pages is not None
+        if self.paged:
+            self._check_paged(model, max_rows, max_len, grow_to, int(kv_pages))
         self.grow_to = int(grow_to or max_len)   # the arena may be re-allocated up to this many positions per slot (default: fixed)
         self.model, self.llm = model, model.llm
         self.rows, self.max_len, self.use_graph = max_rows, max_len, use_graph
         dev = model.device
-        self.arena = self.llm.new_cache(max_rows, max_len, dev)
-        self.staging = self.llm.new_cache(max_rows, max_len, dev)  # batched prefills land here, then move to their slots
+        if self.paged:
+            self.admit_rows = max(1, min(max_rows, int(admit_rows or min(max_rows, 8))))
+            self.max_prompt_len = int(max_prompt_len or min(max_len, 1024))
+            if self.max_prompt_len % 64 or not 0 < self.max_prompt_len <= max_len:
+                raise ValueError("max_prompt_len must be a multiple of 64 in 64..max_len")
+            self.pages = PagePool(int(kv_pages))
+            with self.llm._st("attn"):
+                self.arena = self.llm.new_paged_cache(max_rows, max_len, int(kv_pages), dev)
+            self.staging = self.llm.new_cache(self.admit_rows, self.max_prompt_len, dev)
+        else:
+            self.admit_rows = max_rows
+            self.arena = self.llm.new_cache(max_rows, max_len, dev)
+            self.staging = self.llm.new_cache(max_rows, max_len, dev)  # batched prefills land here, then move to their slots
         self.slots = SlotTable(max_rows)
         self.queue = deque()
         self.live = {}
@@ -158,6 +217,30 @@ class ContinuousBatcher:
         self._side = torch.cuda.Stream(device=dev) if self.overlap else None
         self._placed = None
 
+    @staticmethod
+    def _check_paged(model, max_rows, max_len, grow_to, kv_pages):
+        if grow_to is not None:
+            raise ValueError("grow_to does not apply to a paged KV cache (its pool never moves)")
+        if kv_pages < 1:
+            raise ValueError("kv_pages must be >= 1")
+        n_pos = int(model.config.llm_cfg.max_position_embeddings)
+        if max_len % 64 or not 0 < max_len <= min(8192, n_pos):
+            # (the RoPE tables have exactly max_position_embeddings rows: a position beyond them would read past the table)
+            raise ValueError(f"max_len must be a multiple of 64 and <= min(8192, max_position_embeddings = {n_pos})")
+        llm = model.llm
+        if llm.prec is not None or llm.decode_path(max_rows, max_len) is None:
+            raise ValueError("kv_pages needs a model whose decode step runs on the weight-streaming kernels (a single-type 16-bit or "
+                             "e4m3 stack within the stream limits, <= 64 rows)")
+
+    def kv_stats(self):
+        """paged mode: pages total / free / high water and the bytes of the page pools and of the staging cache"""
+        st = sum(t.numel() * t.element_size() for t in self.staging.k + self.staging.vt)
+        if not self.paged:
+            return dict(pages_total=None, pages_free=None, high_water=None,
+                        pool_bytes=sum(t.numel() * t.element_size() for t in self.arena.k + self.arena.vt), staging_bytes=st)
+        return dict(pages_total=self.pages.n, pages_free=self.pages.n_free, high_water=self.pages.high_water,
+                    pool_bytes=self.arena.nbytes(), staging_bytes=st)
+
     # ------------------------------------------------------------------ admission-time warm-up
     @engine.model_entry(lambda self, *a, **kw: self.model.precision)
     def warm_admission(self, input_ids, image, rows=1):
@@ -169,7 +252,7 @@ class ContinuousBatcher:
             raise RuntimeError("warm_admission() must run before the first admission")
         if self.use_graph and self.graph is None:
             self._capture()
-        k = max(1, min(int(rows), self.rows))
+        k = max(1, min(int(rows), self.admit_rows))
         ids = input_ids.reshape(1, -1).to(I64).cpu().repeat(k, 1)
         imgs = torch.stack([image] * k)
         def once():
@@ -354,6 +437,9 @@ class ContinuousBatcher:
             self.occupied[r.slot] = 1
             self.inv_temp[r.slot] = it
             self.seed[r.slot] = int(r.seed or 0)
+        if self.paged:
+            self._place_pages(reqs, placed, rows)
+            return
         if rows:
             dev = self.tok.device
             src = torch.tensor(rows, dtype=I64, device=dev)
@@ -365,6 +451,65 @@ class ContinuousBatcher:
             for l in range(len(self.arena.k)):
                 self.arena.k[l][:, :, :n].index_copy_(0, dst, self.staging.k[l][:, :, :n].index_select(0, src))
                 self.arena.vt[l][..., : n * sp].index_copy_(0, dst, self.staging.vt[l][..., : n * sp].index_select(0, src))
+
+    def _place_pages(self, reqs, placed, rows):
+        """paged mode, on the decode stream: keep the pages a placed request's prompt + new tokens can reach, give back the rest (and
+        all of them for a request that did not go on), write the rows' block-table entries and move their prompt KV into the pages"""
+        for r in reqs:
+            if r.slot is None:
+                if r.pages:
+                    self.pages.release(r.pages)
+                r.pages = None
+                continue
+            keep = -(-(r.prompt_len + r.max_new_tokens) // 64)
+            if keep < len(r.pages):
+                self.pages.release(r.pages[keep:])
+                r.pages = r.pages[:keep]
+        live = [r for r, _, _, _ in placed if r.slot is not None]
+        if not live:
+            return
+        dev = self.tok.device
+        tab = torch.zeros((len(live), self.arena.table.shape[1]), dtype=I32)
+        for j, r in enumerate(live):
+            tab[j, : len(r.pages)] = torch.tensor(r.pages, dtype=I32)
+        slots = torch.tensor([r.slot for r in live], dtype=I64, device=dev)
+        self.arena.table.index_copy_(0, slots, tab.to(dev))
+        meta = torch.tensor([rows, [r.slot for r in live], [r.prompt_len for r in live]], dtype=I32).to(dev)
+        n = max(r.prompt_len for r in live)
+        for l in range(len(self.arena.k)):
+            ops.kv_scatter_pages(self.staging.k[l], self.staging.vt[l], self.arena.k[l], self.arena.vt[l], self.arena.table, meta,
+                                 min(n, self.max_prompt_len))
+
+    def _take_batch(self):
+        """the requests of the next admission wave, off the head of the queue.  Slot mode: as many as there are free slots.  Paged mode:
+        FIFO while a row is free and the head request's ceil(bound / 64) pages are (reserved here, at the decision); a request that can
+        never fit finishes with `error`, one that does not fit yet waits at the head.  Returns (batch, refused)."""
+        if not self.paged:
+            return [self.queue.popleft() for _ in range(min(len(self.queue), self.slots.n_free))], []
+        batch, refused = [], []
+        while self.queue and len(batch) < min(self.slots.n_free, self.admit_rows):
+            r = self.queue[0]
+            bound = self._bound(r)
+            need = -(-bound // 64)
+            err = None
+            if bound > self.max_len:
+                err = f"the request's context bound {bound} exceeds max_len {self.max_len}"
+            elif need > self.pages.n:
+                err = f"the request's context bound {bound} needs {need} pages, more than the pool's {self.pages.n}"
+            elif bound - r.max_new_tokens > self.max_prompt_len:
+                err = f"the request's prompt bound {bound - r.max_new_tokens} exceeds max_prompt_len {self.max_prompt_len}"
+            if err is not None:
+                self.queue.popleft()
+                r.done, r.error = True, err
+                refused.append(r)
+                continue
+            ids = self.pages.reserve(need)
+            if ids is None:
+                break
+            self.queue.popleft()
+            r.pages = ids
+            batch.append(r)
+        return batch, refused
 
     # ------------------------------------------------------------------ overlapped admission (worker thread + side stream)
     def _launch_admission(self, reqs):
@@ -405,6 +550,9 @@ class ContinuousBatcher:
             for r in job["reqs"]:
                 if not r.done:
                     r.done, r.error = True, f"admission failed: {job['error']}"
+                if r.pages:   # (paged mode: nothing of the wave was placed)
+                    self.pages.release(r.pages)
+                    r.pages = None
             if not isinstance(job["error"], Exception):
                 raise job["error"]
         else:
@@ -426,6 +574,12 @@ class ContinuousBatcher:
             s = r.slot
             self.occupied[s] = 0
             self.pos[s] = 0
+            if self.paged:
+                # the row's entries point at the sink page again (on the decode stream, so before any later _place can
+                # write these pages into another row's entries), then the pages go back to the pool
+                self.arena.table[s].zero_()
+                self.pages.release(r.pages)
+                r.pages = None
             self.slots.release(s)
             r.slot = None
 
@@ -441,14 +595,18 @@ class ContinuousBatcher:
         if self.overlap:
             events += self._finish_admission()
             if self._job is None and self._may_admit():
-                batch = [self.queue.popleft() for _ in range(min(len(self.queue), self.slots.n_free))]
-                self._grow_for(batch)
-                self._launch_admission(batch)
+                batch, refused = self._take_batch()
+                events += [(r.rid, None, True) for r in refused]
+                if batch:
+                    self._grow_for(batch)
+                    self._launch_admission(batch)
             if self._job is not None and not self.slots.active():
                 events += self._finish_admission(wait=True)   # nothing to decode meanwhile: wait for the rows
         elif self._may_admit():
-            batch = [self.queue.popleft() for _ in range(min(len(self.queue), self.slots.n_free))]
-            self._admit(batch)
+            batch, refused = self._take_batch()
+            events += [(r.rid, None, True) for r in refused]
+            if batch:
+                self._admit(batch)
             for r in batch:
                 events.append((r.rid, r.tokens[-1] if r.tokens else None, r.done))
         act = self.slots.active()

@@ -138,6 +138,12 @@ typedef struct gr_gemv_desc {
   int w8; const float* w_scale;
 } gr_gemv_desc;
 int gr_gemv_fused(const gr_gemv_desc* d, hipStream_t stream);
+/* ABI 9, additive -- the QKV stream (epi 3, either weight type) into a PAGED KV cache (the continuous batcher's kv_pages mode):
+ * d->kc is a K pool [pages, H, 64, HD], d->vt a V^T pool [pages, H, HD, 64]; row m's position pos goes to page
+ * block_table[m * table_ld + pos / 64] (int32, table_ld <= 128), at offset pos % 64.  Page 0 is the pool's sink page: unowned table
+ * entries point at it, and a position past the end of the table writes there.  d->kv_stride is ignored.  Every other field and the
+ * values written are gr_gemv_fused's.  GR_EINVAL for epi != 3 and in the operand-pair build. */
+int gr_gemv_fused_paged(const gr_gemv_desc* d, const int* block_table, int table_ld, hipStream_t stream);
 
 /* exact fp32 GEMM (f32-input MFMA): C = act(A.W^T + bias) (+ resid); K % 16 == 0.  DDETR linears
  * (HF 4.32 DeformableDetr* layers used from groma/model/ddetr_transformer.py:299-359). act: 0 | 2 (ReLU) */
@@ -172,6 +178,18 @@ int gr_attention_bf16(const void* q, const void* k, const void* vt, void* out, c
 /* fused-QKV split (+ HF rotate_half RoPE when cos/sin given) into the layouts above / the KV cache */
 int gr_qkv_split(const void* qkv, void* q, void* k, void* vt, const float* cosT, const float* sinT, int B, int H, int L,
                  int head_dim, int pos0, int kv_stride, const int* pos_dev, int pos_stride, hipStream_t stream);
+/* ABI 9, additive: the same for one new position per row (L == 1, else GR_EINVAL) into a paged cache (pools and block table as for
+ * gr_gemv_fused_paged; the decode step of 9..64 rows).  Bit-identical values to gr_qkv_split.  GR_EINVAL in the operand-pair build. */
+int gr_qkv_split_paged(const void* qkv, void* q, void* k_pool, void* vt_pool, const float* cosT, const float* sinT, int B, int H,
+                       int L, int head_dim, int pos0, const int* block_table, int table_ld, const int* pos_dev, int pos_stride,
+                       hipStream_t stream);
+/* ABI 9, additive: admission into a paged cache.  k_src [n_src, H, S, hd] / vt_src [n_src, H, hd, S] (S % 64 == 0: the staging
+ * cache of a batched prefill); entry i < n (device int32 arrays) copies staging row src_rows[i] into the pages of table row
+ * dst_rows[i] (< n_dst), every whole 64-position page below min(lens[i], max_len); max_len <= S and <= table_ld * 64.  Rows out of
+ * range are skipped.  GR_EINVAL in the operand-pair build. */
+int gr_kv_scatter_pages(const void* k_src, const void* vt_src, void* k_pool, void* vt_pool, const int* block_table, int table_ld,
+                        const int* src_rows, const int* dst_rows, const int* lens, int n, int n_src, int n_dst, int H, int S,
+                        int head_dim, int max_len, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------ decode step -- */
 /* One new token per row (groma/model/groma.py:376-379 + HF LlamaDecoderLayer at L = 1): gr_gemv_fused (above) streams each
@@ -186,6 +204,13 @@ int gr_qkv_split(const void* qkv, void* q, void* k, void* vt, const float* cosT,
 int gr_decode_attention(const void* q, const void* k, const void* vt, void* out, const int* kv_len, int B, int H, int Smax,
                         int kv_stride, int head_dim, int q_pos0, float scale, const int* pos_dev, int pos_stride,
                         int nsplit, float* parts, hipStream_t stream);
+/* ABI 9, additive: gr_decode_attention over a paged cache -- k_pool [pages, H, 64, hd], vt_pool [pages, H, hd, 64], row b's key s in
+ * page block_table[b * table_ld + s / 64] (int32; Smax <= table_ld * 64 <= 8192; a row's visible length is clamped to Smax).  Same
+ * arguments otherwise, same out / parts layout (the o-proj merge of x_mode 2 is unchanged) and the same bits as the slot form over the
+ * same keys.  GR_EINVAL in the operand-pair build. */
+int gr_decode_attention_paged(const void* q, const void* k_pool, const void* vt_pool, void* out, const int* kv_len, int B, int H,
+                              int Smax, const int* block_table, int table_ld, int head_dim, int q_pos0, float scale,
+                              const int* pos_dev, int pos_stride, int nsplit, float* parts, hipStream_t stream);
 
 /* ---------------------------------------------------------------------- image preprocessing -- */
 /* PIL Image.resize (BICUBIC, 8-bit fixed point, two passes; groma/eval/run_groma.py:79) on interleaved uint8 RGB, with
