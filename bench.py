@@ -313,6 +313,7 @@ def run_dry_exchange(args, rank, world):
 
 def measure(model, cfg, args, dev, rank, job, P, gen, batch, plan="throughput", steps=None, warmup=None, strong=False, keep=None):
     """time `steps` steps of the hot path at `batch` images per forward call through `job`; returns (seconds, step_fn).
+    job.last_rows: the exchanged rows of the LAST timed step (valid until the next step).
     keep: a dict that receives, as host arrays, what the LAST timed step handed its caller (see dump_arrays)"""
     from groma_amd import synth
     steps = args.steps if steps is None else steps
@@ -352,7 +353,7 @@ def measure(model, cfg, args, dev, rank, job, P, gen, batch, plan="throughput", 
             res = job.exchange(torch.zeros((0, width), dtype=torch.float32, device=dev))
         else:
             res = job.exchange(rows[0] if len(rows) == 1 else torch.cat(rows))
-        if hold:
+        if i == last_timed:
             held["rows"] = res
         return res
 
@@ -368,9 +369,11 @@ def measure(model, cfg, args, dev, rank, job, P, gen, batch, plan="throughput", 
         for i in range(job.setup_steps):
             step(-1 - i)
         elapsed = job.timed(step, warmup, steps, after_warmup=lambda: mark.update(c=caps()))
-        if keep is not None:   # before any further step: graph replays reuse their output buffers
+        # what the exchange delivered at the last timed step; read before any further step: graph replays reuse their output buffers
+        job.last_rows = held.get("rows")
+        if keep is not None:
             keep.update(dump_arrays(held))
-            held.clear()
+        held.clear()
     finally:
         model.gemm_plan = old
     # a hipGraph capture (GraphPool: third sighting of a shape) inside the timed region would put a capture pass and a
@@ -769,21 +772,26 @@ def main():
                     help="split-K plan class of the headline measurement (ops.plan_splits): a function of the layer shape only")
     ap.add_argument("--no-prefill-graphs", action="store_true",
                     help="launch the ViT / LLaMA prefill layers eagerly instead of replaying their captured hipGraphs (A/B)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the benchmark reports: the per-kernel roofline (the same steps "
+                         "again, eagerly, with HIP events), the live PMC traffic passes, `extras` (other batch sizes, plans, precisions, "
+                         "generate), the `parity` block and the CPU baseline.  Off: set up, warm up, time the steps, dump, print")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the `parity` block (the benchmarked mode against the unchained fp32 oracle on the bench's own inputs at "
-                         "reduced depth: N = 1, rank 0, after the timed region)")
+                    help="with --full: skip the `parity` block (the benchmarked mode against the unchained fp32 oracle on the bench's own "
+                         "inputs at reduced depth: N = 1, rank 0, after the timed region)")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the live rocprofv3 PMC passes for roofline.traffic (the committed profiles/ summary is reported instead)")
+                    help="with --full: skip the live rocprofv3 PMC passes for roofline.traffic (the committed profiles/ summary is reported instead)")
     ap.add_argument("--generate-traffic", action="store_true",
-                    help="--mode generate: also run the rocprofv3 PMC passes for the stream kernel's traffic (OFF by default: the profiler crashes or hangs "
+                    help="with --full --mode generate: also run the rocprofv3 PMC passes for the stream kernel's traffic (OFF by default: the profiler crashes or hangs "
                          "on the generate run on this image -- round 6 lost two 5-minute timeouts to it; the round-5 figure stands: 103.7 MB per launch against 102.5 algorithmic)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the `extras` block (1 and 4 images per call, greedy generate, e4m3 operands: measured after the "
+                    help="with --full: skip the `extras` block (1 and 4 images per call, greedy generate, e4m3 operands: measured after the "
                          "headline's timed region, N = 1 only)")
     ap.add_argument("--cpu-baseline-reps", type=int, default=3,
-                    help="timed full-depth oracle forwards after the reduced-depth warm-up; the median is reported (BASELINE.md 3)")
-    ap.add_argument("--gemm-breakdown", default=None, help="write a per-shape GEMM table (from the HIP-event hook) here")
+                    help="with --full: timed full-depth oracle forwards after the reduced-depth warm-up; the median is reported (BASELINE.md 3)")
+    ap.add_argument("--gemm-breakdown", default=None,
+                    help="with --full: write a per-shape GEMM table (from the HIP-event hook of the roofline leg) here")
     ap.add_argument("--host-glue", action="store_true",
                     help="with --dry-exchange: every rank also runs the forward's real host-side glue (CPU-RNG shuffles, placeholder "
                          "splice, scatter-row lists) per step and the JSON reports its microseconds per step under N-way host contention")
@@ -794,6 +802,8 @@ def main():
                     help="launcher / process-group / exchange / timing path only, with synthetic rows on CPU (gloo); no model")
     args = ap.parse_args()
 
+    if args.gemm_breakdown and not args.full:
+        ap.error("--gemm-breakdown needs --full (the table comes from the roofline leg)")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -851,13 +861,74 @@ def main():
         os.makedirs(args.dump_outputs, exist_ok=True)
         for name, a in dumped.items():
             np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
-    gathered = step(args.warmup + args.steps)  # one more (untimed) step: what the exchange delivered
+    gathered = job.last_rows   # what the exchange delivered at the last timed step
     exchanged_regions = int(gathered[:, -1].sum().item())
+    n_reg = [b.shape[0] for b in model._last_aux["sel_idx"]] if job.rows else [100]
+    fl = flops_per_image(cfg, sum(n_reg) / len(n_reg), P)
+    ips = job.global_batch * args.steps / elapsed
+    peak = 5000.0 if fp8 else 2500.0  # dense MFMA peak of the operand type (MI355X_MICROARCH.md)
+    out = {
+        "metric": "images/sec end-to-end forward (448px, 300 proposals, 128 tok)",
+        "value": ips, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype, "data": "synthetic",
+        "dtype_note": ("IEEE half operands (f32 accumulate, fp32 residual streams) behind a pair-operand ViT: same MFMA rate and bytes as BASELINE's bf16, 3 more "
+                       "mantissa bits -- full-depth logits 3.3e-3 from the reference's fp32 pass instead of bf16's 2.6e-2 (profiles/r06_precision_ablation.txt); "
+                       "the bf16 builds are in extras / summary_tail (--full)") if args.dtype == "fp16" else None,
+        "rccl_ranks": rccl_ranks,  # all-reduce of ones over the process group: the ranks that actually took part
+        # the slowest / fastest rank's own time per step (max is what `value` is computed from): load imbalance across ranks
+        "ms_per_step_rank_max": job.last_elapsed_max / args.steps * 1e3, "ms_per_step_rank_min": job.last_elapsed_min / args.steps * 1e3,
+        "graph_captures_in_timed_region": job.captures_in_timed_region, "graph_setup_steps": getattr(job, "setup_steps", 0),
+        "host_threads_per_rank": host_threads,
+        "full": args.full,
+        "exchange": {"collective": "one all_gather_into_tensor per step" if use_dist else "none (single process)",
+                     "row_f32": {"head": head_w, "pred_boxes": ROW_BOXES, "n_regions": 1},
+                     "rows_gathered": int(gathered.shape[0]), "regions_gathered": exchanged_regions},
+        "config": {"workload": "configs[2]: full Groma-7B forward (DINOv2-L + DDETR 300 proposals -> NMS 100 regions + "
+                               "region encoder + Vicuna-7B prefill, logits for all positions), random-init weights"
+                               if args.config == "7b" else "tiny parity architecture (NOT the headline workload)",
+                   "images_per_gpu": job.rows, "images_per_forward_call": min(args.batch, job.rows),
+                   "global_batch": job.global_batch, "prompt_tokens": P,
+                   "llm_seq_len": fl["L"], "regions_per_image": sum(n_reg) / len(n_reg),
+                   "precision": model.mode,
+                   "vit_operands": ("(hi, lo) pairs of halves, 3 MFMA passes per contraction (libgroma_hip_ref.so): the index-valued results of "
+                                    "this build equal the fp32 reference's, unchained" if model.vit_precision == "ref" else "same as dtype"),
+                   "gemm_plan": args.gemm_plan, "prefill_graphs": not args.no_prefill_graphs,
+                   "parallelism": f"dp{world} (image batch sharded, full replica per GPU)"},
+        # the flop model over the headline's own time; the per-kernel figures need a leg of their own (--full)
+        "roofline": {"bound": "mfma", "peak": peak, "unit": "TFLOP/s",
+                     "e2e_algorithmic_tflops_per_gpu": fl["total"] * job.rows * args.steps / elapsed / 1e12,
+                     "e2e_frac_of_peak": fl["total"] * job.rows * args.steps / elapsed / 1e12 / peak},
+    }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "step": args.warmup + args.steps - 1,
+                               "arrays": {k: [str(a.dtype)] + list(a.shape) for k, a in dumped.items()},
+                               "bytes": sum(a.nbytes for a in dumped.values())}
+    if gen:
+        out["metric"] = "images/sec greedy generate (448px, 300 proposals, 128-token prompt, %d new tokens)" % args.new_tokens
+        out["config"]["workload"] = ("configs[3]: generate() = full Groma-7B prefill + %d greedy decode steps (hipGraph replay), "
+                                     "random-init weights, no EOS" % args.new_tokens)
+        out["config"]["new_tokens"] = args.new_tokens
+        del out["roofline"]   # a forward's flop model says nothing about the decode steps: their HBM roofline is --full's
+    if args.full:
+        out = full_legs(out, model, cfg, args, dev, rank, world, job, step, elapsed, fl, P, fp8, gen)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if use_dist:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def full_legs(out, model, cfg, args, dev, rank, world, job, step, elapsed, fl, P, fp8, gen):
+    """--full: everything the JSON line carries beyond the headline, each leg after (outside) the timed region -- the roofline leg
+    (the headline's steps again, eagerly, with HIP events around every GEMM launch), the PMC traffic passes, and on rank 0 of a
+    one-GPU run the `extras`, `parity` and `cpu_baseline` blocks.  Every rank runs the roofline leg (its steps exchange)."""
+    from groma_amd import engine
+    from groma_amd import synth as _synth
     model.gemm_plan = args.gemm_plan
 
     # ---- roofline leg: the same steps again with HIP events around every GEMM launch (on the launch stream) ----
-    n_reg = [b.shape[0] for b in model._last_aux["sel_idx"]] if job.rows else [100]
-    fl = flops_per_image(cfg, sum(n_reg) / len(n_reg), P)
     # HIP events cannot bracket launches inside a replayed graph (the hook sits in the launch functions): time the same
     # kernels eagerly
     model.decode_graph = False
@@ -901,67 +972,30 @@ def main():
                 traffic_source = "committed summary of the same rocprofv3 passes: profiles/" + os.path.basename(cands[-1])
         except Exception:
             traffic = None
-    ips = job.global_batch * args.steps / elapsed
-    peak = 5000.0 if fp8 else 2500.0  # dense MFMA peak of the operand type (MI355X_MICROARCH.md)
+    ips = out["value"]
+    peak = 5000.0 if fp8 else 2500.0
     kname = "gemm_fp8_256_kernel(GemmArgs) -- 256x256 ping-pong e4m3 MFMA GEMM" if fp8 else \
         "gemm_bf16_256_kernel(GemmArgs) -- 256x256 ping-pong MFMA GEMM incl. implicit-GEMM 3x3 convs"
     achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    out = {
-        "metric": "images/sec end-to-end forward (448px, 300 proposals, 128 tok)",
-        "value": ips, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
-        "dtype_note": ("IEEE half operands (f32 accumulate, fp32 residual streams) behind a pair-operand ViT: same MFMA rate and bytes as BASELINE's bf16, 3 more "
-                       "mantissa bits -- full-depth logits 3.3e-3 from the reference's fp32 pass instead of bf16's 2.6e-2 (profiles/r06_precision_ablation.txt); "
-                       "the bf16 builds are in extras / summary_tail") if args.dtype == "fp16" else None,
-        "rccl_ranks": rccl_ranks,  # all-reduce of ones over the process group: the ranks that actually took part
-        # the slowest / fastest rank's own time per step (max is what `value` is computed from): load imbalance across ranks
-        "ms_per_step_rank_max": job.last_elapsed_max / args.steps * 1e3, "ms_per_step_rank_min": job.last_elapsed_min / args.steps * 1e3,
-        "graph_captures_in_timed_region": job.captures_in_timed_region, "graph_setup_steps": getattr(job, "setup_steps", 0),
-        "host_threads_per_rank": host_threads,
-        "exchange": {"collective": "one all_gather_into_tensor per step" if use_dist else "none (single process)",
-                     "row_f32": {"head": head_w, "pred_boxes": ROW_BOXES, "n_regions": 1},
-                     "rows_gathered": int(gathered.shape[0]), "regions_gathered": exchanged_regions},
-        "config": {"workload": "configs[2]: full Groma-7B forward (DINOv2-L + DDETR 300 proposals -> NMS 100 regions + "
-                               "region encoder + Vicuna-7B prefill, logits for all positions), random-init weights"
-                               if args.config == "7b" else "tiny parity architecture (NOT the headline workload)",
-                   "images_per_gpu": job.rows, "images_per_forward_call": min(args.batch, job.rows),
-                   "global_batch": job.global_batch, "prompt_tokens": P,
-                   "llm_seq_len": fl["L"], "regions_per_image": sum(n_reg) / len(n_reg),
-                   "precision": model.mode,
-                   "vit_operands": ("(hi, lo) pairs of halves, 3 MFMA passes per contraction (libgroma_hip_ref.so): the index-valued results of "
-                                    "this build equal the fp32 reference's, unchained" if model.vit_precision == "ref" else "same as dtype"),
-                   "gemm_plan": args.gemm_plan, "prefill_graphs": not args.no_prefill_graphs,
-                   "parallelism": f"dp{world} (image batch sharded, full replica per GPU)"},
-        "roofline": {"bound": "mfma", "kernel": kname,
-                     "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic,
-                     "traffic_note": ("bytes/launch of gemm_bf16_256_kernel at the L2<->fabric boundary (Infinity-Cache hits "
-                                      "included; DESIGN.md 3a); " + traffic_source) if traffic else None,
-                     "launches_per_step": gemm_launches / max(args.steps, 1),
-                     "avg_launch_us": gemm_ms * 1e3 / max(gemm_launches, 1),
-                     "flops_per_launch": gemm_flops / max(gemm_launches, 1),
-                     "kernel_time_share_of_step": (gemm_ms / args.steps) / (elapsed / args.steps * 1e3),
-                     "all_gemm_kernels": {"achieved": all_flops / (all_ms * 1e-3) / 1e12 if all_ms > 0 else 0.0,
-                                          "launches_per_step": len(recs) / max(args.steps, 1),
-                                          "time_share_of_step": (all_ms / args.steps) / (elapsed / args.steps * 1e3)},
-                     "e2e_algorithmic_tflops_per_gpu": fl["total"] * job.rows * args.steps / elapsed / 1e12,
-                     "e2e_frac_of_peak": fl["total"] * job.rows * args.steps / elapsed / 1e12 / peak},
-    }
-    if dumped is not None:
-        out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "step": args.warmup + args.steps - 1,
-                               "arrays": {k: [str(a.dtype)] + list(a.shape) for k, a in dumped.items()},
-                               "bytes": sum(a.nbytes for a in dumped.values())}
+    out["roofline"] = {"bound": "mfma", "kernel": kname,
+                       "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic,
+                       "traffic_note": ("bytes/launch of gemm_bf16_256_kernel at the L2<->fabric boundary (Infinity-Cache hits "
+                                        "included; DESIGN.md 3a); " + traffic_source) if traffic else None,
+                       "launches_per_step": gemm_launches / max(args.steps, 1),
+                       "avg_launch_us": gemm_ms * 1e3 / max(gemm_launches, 1),
+                       "flops_per_launch": gemm_flops / max(gemm_launches, 1),
+                       "kernel_time_share_of_step": (gemm_ms / args.steps) / (elapsed / args.steps * 1e3),
+                       "all_gemm_kernels": {"achieved": all_flops / (all_ms * 1e-3) / 1e12 if all_ms > 0 else 0.0,
+                                            "launches_per_step": len(recs) / max(args.steps, 1),
+                                            "time_share_of_step": (all_ms / args.steps) / (elapsed / args.steps * 1e3)},
+                       "e2e_algorithmic_tflops_per_gpu": fl["total"] * job.rows * args.steps / elapsed / 1e12,
+                       "e2e_frac_of_peak": fl["total"] * job.rows * args.steps / elapsed / 1e12 / peak}
     if vit_recs is not None:
         out["roofline"]["vit_pair_gemms"] = pair_block(vit_recs, args.steps)
     if gen:  # configs[3]: the decode steps stream the bf16 weights once per token -> HBM roofline of the GEMV kernel
         gv = [r for r in recs if r[3] & 8]
         gv_ms = sum(r[4] for r in gv)
         gv_bytes = sum((1.0 if r[3] & 16 else 2.0) * r[1] * r[2] for r in gv)  # algorithmic bytes per launch: the N x K weight (16-bit, or e4m3 bytes: tag 16), read once
-        out["metric"] = "images/sec greedy generate (448px, 300 proposals, 128-token prompt, %d new tokens)" % args.new_tokens
-        out["config"]["workload"] = ("configs[3]: generate() = full Groma-7B prefill + %d greedy decode steps (hipGraph replay), "
-                                     "random-init weights, no EOS" % args.new_tokens)
-        out["config"]["new_tokens"] = args.new_tokens
         ach = gv_bytes / (gv_ms * 1e-3) / 1e9 if gv_ms > 0 else 0.0
         gv_traffic = None
         if rank == 0 and world == 1 and not args.no_traffic and args.generate_traffic and args.config == "7b" and not fp8:
@@ -987,7 +1021,6 @@ def main():
             out = dict(list(out.items())[:5] + [("extras_summary", summ)] + list(out.items())[5:])
         if world == 1 and not args.no_parity and not gen and args.config == "7b":
             try:   # the benchmarked MODE against the oracle on the bench's own inputs (reduced depth; see parity_block)
-                from groma_amd import synth as _synth
                 p_im, p_ids = _synth.make_inputs(cfg, model, job.rows, seed=1234 + rank, prompt_len=P)   # exactly what measure() timed
                 out["parity"] = parity_block(model.mode.replace("+e4m3", ""), fp8, p_im[:4].to(dev), p_ids[:4].to(dev), seed=1000 + args.warmup)
             except Exception as e:
@@ -1008,10 +1041,7 @@ def main():
                                    "parity": {k: out.get("parity", {}).get(k) for k in ("n_images", "images_with_all_index_results_equal", "near_tie_images", "unexplained_images",
                                                                                         "logits_rel_l2", "logits_tolerance", "within_tolerance")},
                                    "extras [images/s, roofline frac]": out["extras_summary"]}
-        print(json.dumps(out), flush=True)
-    if use_dist:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

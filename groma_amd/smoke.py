@@ -23,7 +23,7 @@ def run_smoke():
     # image seed 648: the first committed UNCHAINED fixture at this width (tests/golden/e2e_seeds.json: the oracle's smallest adjacent gap
     # among its top-301 class logits is 1.4e-4, ~10x the distance between two fp32 evaluations of the proposer), so the torch.equal
     # assertions on index-valued results below are decided by the implementation, never by a near-tie (what happens on unselected
-    # seeds is measured: profiles/r06_index_survival.txt, and reported per run by bench.py's `parity` block)
+    # seeds is measured: profiles/r06_index_survival.txt, and reported per run by `bench.py --full`'s `parity` block)
     images, ids = synth.make_inputs(cfg, model, bs=1, seed=648)
     torch.manual_seed(3)
     out = model.forward(input_ids=ids.clone(), images=images, return_dict=True)

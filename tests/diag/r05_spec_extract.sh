@@ -9,7 +9,7 @@ cat $O/spec_extract_ab.txt
 (timeout 1500 python -m pytest tests -q -m gpu --timeout 900 2>&1 | tail -30 > $O/gpu_tests.log)
 (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1)
 t0=$(date +%s)
-(timeout 900 python bench.py --gemm-breakdown $O/gemm_shapes_b14.txt > $O/bench.json 2> $O/bench.err)
+(timeout 900 python bench.py --full --gemm-breakdown $O/gemm_shapes_b14.txt > $O/bench.json 2> $O/bench.err)
 echo "wall seconds: $(( $(date +%s) - t0 ))" > $O/bench_wall.txt
-bash tests/diag/timeline_run.sh $T hybrid
+bash tests/diag/timeline_run.sh $O hybrid
 tail -4 $O/gpu_tests.log; tail -3 $O/smoke.log; head -c 1100 $O/bench.json; echo; cat $O/bench_wall.txt; head -12 $O/timeline_hybrid.txt; grep -A6 "largest idle" $O/timeline_hybrid.txt

@@ -89,3 +89,12 @@ def test_host_glue_under_8_way_contention():
     assert d["rccl_ranks"] == 8 and g8["images_per_rank"] == 14 and d["exchange_ok"]
     assert 0 < g8["host_glue_us_per_step_rank_min"] <= g8["host_glue_us_per_step_rank_max"]
     assert g8["host_glue_us_per_step_rank_max"] < 20000      # < 20 ms even with 8 python ranks on the 8 cores of this container
+
+
+def test_full_only_options_are_refused_on_a_plain_run():
+    """a plain run measures the headline only; an option that only the legs behind --full can serve fails up front instead of
+    quietly writing nothing"""
+    assert "--full" in _run(["--help"]).stdout
+    r = _run(["--gpus", "1", "--steps", "1", "--warmup", "0", "--gemm-breakdown", os.devnull])
+    assert r.returncode != 0 and "--gemm-breakdown needs --full" in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
