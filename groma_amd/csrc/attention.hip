@@ -675,13 +675,9 @@ extern "C" int gr_attention_bf16(const void* q, const void* k, const void* vt, v
   p.causal = causal; p.q_pos0 = q_pos0;
   p.scale_log2 = scale * 1.44269504088896340736f;
   dim3 grid(B * H, gr_cdiv(Lq, 128));
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)attention_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * GR_SPW) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attention_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * GR_SPW) != hipSuccess)
-      return GR_EINVAL;
-    attr_set = true;
-  }
+  if (gr_set_max_lds((const void*)attention_kernel<128>, 65536 * GR_SPW) != hipSuccess ||
+      gr_set_max_lds((const void*)attention_kernel<64>, 32768 * GR_SPW) != hipSuccess)
+    return GR_EINVAL;
   if (head_dim == 128) hipLaunchKernelGGL(attention_kernel<128>, grid, dim3(256), 65536 * GR_SPW, stream, p);
   else if (head_dim == 64) hipLaunchKernelGGL(attention_kernel<64>, grid, dim3(256), 32768 * GR_SPW, stream, p);
   else return GR_EINVAL;

@@ -233,14 +233,9 @@ __global__ __launch_bounds__(640) void mha32_mfma_kernel(const float* __restrict
 extern "C" int gr_mha32_f32(const float* qk, const float* v, float* out, int B, int Q, int heads, int ldqk, float scale,
                             hipStream_t stream) {
   if (!qk || !v || !out || B <= 0 || Q <= 0 || Q > 1024) return GR_EINVAL;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)mha32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)mha32_mfma_kernel<20>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  hipError_t e = gr_set_max_lds((const void*)mha32_kernel, 160 * 1024);
+  if (e == hipSuccess) e = gr_set_max_lds((const void*)mha32_mfma_kernel<20>, 96 * 1024);
+  if (e != hipSuccess) return (int)e;
   const bool aligned = (ldqk & 3) == 0 && ((((uintptr_t)qk) | ((uintptr_t)v) | ((uintptr_t)out)) & 15) == 0;
   if (Q <= 320 && aligned) {  // the reference's 300 queries: MFMA kernel, 160 queries per block
     constexpr int NKT = 20;

@@ -3,9 +3,10 @@
 // consumer fused in); what is left between the weight streams is this kernel: the 128-query-row MFMA attention tile (1 useful
 // row) replaced by a one-block-per-(row, head) dot-product kernel, optionally over key slices that the o-proj stream merges.
 //   gr_decode_attention   : softmax(q K^T * scale) V over the cache, one block per (row, head[, key slice])
-//   gr_decode_attention_paged : the same over a paged cache (64-position pages reached through a per-row block table)
+//   gr_decode_attention_paged : the same over a paged cache (KV_PAGE-position pages reached through a per-row block table)
 // Positions come from device memory when pos_dev is given (hipGraph replay / ragged continuous batching).
 #include "gr_common.h"
+#include "kv_layout.h"
 #include "../../include/groma_hip.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -22,10 +23,10 @@
 // keys, but only HD / DS rows of V^T.  At 4 rows x 32 heads that is 256 blocks on 256 CUs instead of 128, each streaming 224 KB
 // instead of 300 KB, and -- unlike key slices -- nothing to merge: a block writes its dims of the context directly.
 //
-// PAGED (the continuous batcher's paged cache): k is a pool [pages, H, 64, HD], vt a pool [pages, H, HD, 64], and key s of row b
-// lives in page table[b * table_ld + s / 64] at offset s % 64; kv_stride is then the row's capacity (table_ld * 64), to which the
-// visible length is clamped.  The row's table (<= DEC_SMAX / 64 ints) is staged in LDS behind the scores when the block starts.  Key
-// slices start on 64-aligned keys and an 8-key chunk starts on a multiple of 8, so neither crosses a page.
+// PAGED (the continuous batcher's paged cache, kv_layout.h): k and vt are the page pools; kv_stride is then the row's capacity
+// (table_ld * KV_PAGE), to which the visible length is clamped.  The row's table (<= DEC_SMAX / KV_PAGE ints) is staged in LDS behind
+// the scores when the block starts.  Key slices start on 64-aligned keys and an 8-key chunk starts on a multiple of 8, so neither
+// crosses a page.
 template <int HD, int DS, bool PAGED = false>
 __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                                const bf16_t* __restrict__ vt, bf16_t* __restrict__ out,
@@ -46,18 +47,18 @@ __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __
   const int sb = z * chunk;
   const int S = max(0, min(Sall, sb + chunk) - sb);
   const int Spad = (S + 63) & ~63;
-  const bf16_t* Kp = k + ((long)bh * kv_stride + sb) * HD;
-  const bf16_t* Vp = vt + (long)bh * HD * kv_stride + sb;
+  const bf16_t* Kp = k + kv_k_slot(bh, sb, 0, HD, kv_stride);
+  const bf16_t* Vp = vt + kv_vt_slot(bh, sb, 0, HD, kv_stride);
   int* tbl = (int*)(sc + sc_len);
   if constexpr (PAGED) {
-    const int np = (Sall + 63) >> 6;
+    const int np = kv_page_idx(Sall + KV_PAGE - 1);
     for (int i = tid; i < np; i += 1024) tbl[i] = table[(long)b * table_ld + i];
     __syncthreads();
   }
   // PAGED: 16-B chunk of K row s (this slice's numbering) at dims j8.., and of V^T row d at keys s0..s0+7
   auto kpage = [&](int s, int j8) -> const bf16_t* {
     const int a = sb + s;
-    return k + (((long)tbl[a >> 6] * H + (bh - b * H)) * 64 + (a & 63)) * HD + j8;
+    return k + kv_k_paged(tbl[kv_page_idx(a)], H, bh - b * H, a, j8, HD);
   };
 
   // All global loads of a round are issued before anything consumes them (one exposed memory latency per round of
@@ -68,10 +69,10 @@ __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __
   constexpr int TPD = 1024 / HDB;      // threads per output dim (8 / 16; twice that with DS = 2)
   const int j = tid % LPK, g = tid / LPK;
   const int d = (int)blockIdx.z * HDB + tid / TPD, part = tid % TPD;
-  const bf16_t* vrow = Vp + (long)d * kv_stride;
+  const bf16_t* vrow = Vp + (long)d * kv_stride;  // V^T row d of the slice (kv_vt_slot(bh, sb, d, ..), summed in this order)
   auto vpage = [&](int s0) -> const bf16_t* {
     const int a = sb + s0;
-    return vt + (((long)tbl[a >> 6] * H + (bh - b * H)) * HD + d) * 64 + (a & 63);
+    return vt + kv_vt_paged(tbl[kv_page_idx(a)], H, bh - b * H, a, d, HD);
   };
   const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   float qf[8];
@@ -189,17 +190,17 @@ extern "C" int gr_decode_attention(const void* q, const void* k, const void* vt,
   return GR_OK;
 }
 
-// Paged form: k_pool [pages, H, 64, hd], vt_pool [pages, H, hd, 64]; row b's key s in page block_table[b * table_ld + s / 64].
+// Paged form (kv_layout.h): k_pool and vt_pool are the page pools, block_table row b is batch row b's table.
 extern "C" int gr_decode_attention_paged(const void* q, const void* k_pool, const void* vt_pool, void* out, const int* kv_len, int B,
                                          int H, int Smax, const int* block_table, int table_ld, int head_dim, int q_pos0, float scale,
                                          const int* pos_dev, int pos_stride, int nsplit, float* parts, hipStream_t stream) {
   if (GR_SP) return GR_EINVAL;
   if (!q || !k_pool || !vt_pool || !out || !block_table || B <= 0 || H <= 0 || Smax <= 0 || Smax > DEC_SMAX) return GR_EINVAL;
-  if (table_ld <= 0 || table_ld > DEC_SMAX / 64 || Smax > table_ld * 64) return GR_EINVAL;
+  if (table_ld <= 0 || table_ld > DEC_SMAX / KV_PAGE || Smax > table_ld * KV_PAGE) return GR_EINVAL;
   if (nsplit < 1 || nsplit > 16 || (nsplit > 1 && !parts)) return GR_EINVAL;
   if (!pos_dev && (q_pos0 < 0 || q_pos0 + 1 > Smax)) return GR_EINVAL;
   const int sc_len = (Smax + 63) & ~63;
-  const size_t lds = (size_t)sc_len * sizeof(float) + (size_t)(sc_len / 64) * sizeof(int);
+  const size_t lds = (size_t)sc_len * sizeof(float) + (size_t)(sc_len / KV_PAGE) * sizeof(int);
   const int ds = B * H * nsplit <= DA_DSPLIT_MAX_BLOCKS ? 2 : 1;
   // kv_stride carries the row capacity (Smax): the visible length of a row never reaches past its table
 #define LAUNCH_DAP(HDV, DSV)                                                                                                     \

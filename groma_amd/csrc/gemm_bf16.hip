@@ -352,12 +352,7 @@ extern "C" int gr_gemm_bf16(const gr_gemm_desc* d, hipStream_t stream) {
   p.yield = g_gemm_yield;
   p.tiles_m = gr_cdiv(p.M, use256 ? pp_rows : BM);
   p.tiles_n = gr_cdiv(p.N, use256 ? 256 : BN);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (hipError_t e = gr_set_max_lds((const void*)gemm_bf16_kernel, 65536); e != hipSuccess) return (int)e;
   dim3 grid(p.tiles_m * p.tiles_n, splits);
   ProfRec rec;
   if (g_prof_on) {

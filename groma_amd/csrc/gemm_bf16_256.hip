@@ -444,23 +444,15 @@ int G256_LAUNCH(const GemmArgs& p, hipStream_t stream) {
 int G256_LAUNCH(const GemmArgs& p, hipStream_t stream, int tile_rows) {  // tile_rows: 256 | 192 (p.tiles_m counts tiles of that height)
 #endif
   if (tile_rows != 256 && tile_rows != 192) return GR_EINVAL;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)G256_KERNEL<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
+  hipError_t e = gr_set_max_lds((const void*)G256_KERNEL<8>, 2 * STAGE_BYTES);
 #if !G256_FP8
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)G256_KERNEL<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
+  if (e == hipSuccess) e = gr_set_max_lds((const void*)G256_KERNEL<6>, 2 * STAGE_BYTES);
 #endif
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  if (e != hipSuccess) return (int)e;
   // persistent launch: one block per CU (the 128 KB of LDS allow one block per CU anyway), fewer when there are fewer tiles
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return GR_EINVAL;
-    n_cu = prop.multiProcessorCount > 8 ? (prop.multiProcessorCount & ~7) : 8;
-  }
+  const int cus = gr_cu_count();
+  if (cus < 0) return GR_EINVAL;
+  const int n_cu = cus > 8 ? (cus & ~7) : 8;
 #ifdef G256_NO_PERSIST  // diagnostic build (tests/diag/build_variant.py name -DG256_NO_PERSIST): one tile per workgroup
   const bool persist_off = true;
 #else

@@ -226,11 +226,7 @@ extern "C" int gr_diag_skinny_kw(int kw) {
 template <int NB, int KW>
 static int launch_skinny(const GemmArgs& p, hipStream_t stream) {
   const size_t lds = 2 * (size_t)NB * 16 * SK_SB * KW;
-  static bool attr_set = false;
-  if (!attr_set && lds > 65536) {
-    if (hipFuncSetAttribute((const void*)gemm_skinny_kernel<NB, KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return GR_EINVAL;
-    attr_set = true;
-  }
+  if (lds > 65536 && gr_set_max_lds((const void*)gemm_skinny_kernel<NB, KW>, (int)lds) != hipSuccess) return GR_EINVAL;
   hipLaunchKernelGGL((gemm_skinny_kernel<NB, KW>), dim3(gr_cdiv(p.N, 64 / KW)), dim3(256), lds, stream, p);
   return GR_OK;
 }

@@ -21,8 +21,9 @@
 //     accumulators meet in LDS in a fixed order (bit-reproducible, independent of the other batch rows);
 //   * 16 rows per group, THREE persistent workgroups per CU (<= 168 VGPRs -- the prologue lives beside the two slices already in flight --, 16-45 KB of LDS): a launch is then close to
 //     bytes / bandwidth + one ramp instead of rounds x latency.
-// The epilogue dequantises acc * w_scale[n] * s[m] (the e4m3 GEMM epilogue's order) and then is the 16-bit stream's: f32 out, in-place
-// residual update, SwiGLU over interleaved (gate, up) rows (both in one lane), or RoPE + q / K row / V^T column (partner row 32 lanes away).
+// The epilogue dequantises acc * w_scale[n] * s[m] (the e4m3 GEMM epilogue's order) and then stores through the 16-bit stream's helpers
+// (gemv_args.h): f32 out, in-place residual update, SwiGLU over interleaved (gate, up) rows (both in one lane), or RoPE + q / K row /
+// V^T column (partner row 32 lanes away).
 #include <type_traits>
 
 #include "gemv_args.h"
@@ -55,20 +56,12 @@ __global__ __launch_bounds__(256, G8_WG_PER_CU) void gemv_fp8_kernel(GemvFArgs p
   const int ngroups = p.N / ROWS;
   const uint8_t* W = (const uint8_t*)p.W;
 
-  // ---- a group's 16 rows: two runs of 8 (epi 3: 8 dims d and their rotate_half partners d + HD/2 of one head; else consecutive)
+  // ---- a group's 16 rows: two runs of 8 (gemv_group_rows)
   int r_lo, r_hi;
   const uint8_t* row_ptr;  // this lane's row fr of the current group
   auto set_group = [&](int g) {
-    r_lo = g * ROWS;
-    r_hi = g * ROWS + ROWS / 2;
-    if (p.epi == 3 && (long)g * ROWS < 2L * p.H * p.HD) {
-      const int bph = p.HD / ROWS;  // groups per head
-      const int hh = g / bph, j = g - hh * bph;
-      r_lo = hh * p.HD + j * (ROWS / 2);
-      r_hi = r_lo + p.HD / 2;
-    }
-    const int n = fr < ROWS / 2 ? r_lo + fr : r_hi + (fr - ROWS / 2);
-    row_ptr = W + (long)n * p.ldw + fg * 16;
+    gemv_group_rows<ROWS>(p, g, r_lo, r_hi);
+    row_ptr = W + (long)gemv_row<ROWS>(r_lo, r_hi, fr) * p.ldw + fg * 16;
   };
   const int ns = (p.K + G8_KS - 1) / G8_KS;  // K slices; wave w takes w, w + 4, ...
   const int cnt = wave < ns ? (ns - wave + 3) / 4 : 0;
@@ -242,29 +235,10 @@ __global__ __launch_bounds__(256, G8_WG_PER_CU) void gemv_fp8_kernel(GemvFArgs p
     if constexpr (MB > RB) batch(RB, std::false_type{});
     __syncthreads();
   } else {  // x_mode 2: merge the key slices of decode_attention (slice order; rounded like its nsplit = 1 output), then quantise
-    const int hd = p.a_hd, c8 = p.K >> 3;
+    const int c8 = p.K >> 3;
     for (int idx = tid; idx < MB * c8; idx += 256) {
       const int m = idx / c8, k0 = (idx - m * c8) << 3;
-      union { bf16x8 v; uint32_t u[4]; } pk;
-      pk.v = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-      if (m < p.M) {
-        const int hh = k0 / hd, dd = k0 - hh * hd;
-        const float* base = p.a_parts + ((long)(m * (p.K / hd) + hh) * p.a_nsplit) * (hd + 2);
-        float mx = -1e30f;
-        for (int i = 0; i < p.a_nsplit; ++i) mx = fmaxf(mx, base[i * (hd + 2) + hd]);
-        float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, l = 0.f;
-        for (int i = 0; i < p.a_nsplit; ++i) {
-          const float* bi = base + i * (hd + 2);
-          const float f = __expf(bi[hd] - mx);
-          l += f * bi[hd + 1];
-          const f32x4 o0 = *(const f32x4*)(bi + dd), o1 = *(const f32x4*)(bi + dd + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { o[e] += f * o0[e]; o[4 + e] += f * o1[e]; }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pk.u[e] = pack2bf(o[2 * e] / l, o[2 * e + 1] / l);
-      }
-      *(bf16x8*)(tmp16 + (long)m * p.K + k0) = pk.v;
+      *(bf16x8*)(tmp16 + (long)m * p.K + k0) = gemv_merge8(p, m, k0);
     }
     first_slices();  // (behind the merge's own global reads; the quantising passes below read LDS only)
     __syncthreads();
@@ -321,55 +295,30 @@ __global__ __launch_bounds__(256, G8_WG_PER_CU) void gemv_fp8_kernel(GemvFArgs p
       int n[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int rr = 4 * fg + r;
-        n[r] = rr < ROWS / 2 ? e_lo + rr : e_hi + (rr - ROWS / 2);
+        n[r] = gemv_row<ROWS>(e_lo, e_hi, 4 * fg + r);
         y[r] = v[r] * p.w_scale[n[r]] * sx;  // dequantise: acc * w_scale[n] * a_scale[m], the e4m3 GEMM epilogue's order
       }
       if (p.epi == 0) {
         if (ok)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) ((float*)p.C)[(long)m * p.ldc + n[r]] = y[r];
+          for (int r = 0; r < 4; ++r) gemv_store_f32(p, m, n[r], y[r]);
       } else if (p.epi == 1) {
         if (ok)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) p.resid[(long)m * p.ldr + n[r]] += y[r];
-      } else if (p.epi == 2) {  // interleaved rows: even = gate_j, odd = up_j -- both in this lane
+          for (int r = 0; r < 4; ++r) gemv_add_resid(p, m, n[r], y[r]);
+      } else if (p.epi == 2) {  // gate and up rows both in this lane
         if (ok) {
-          ((bf16_t*)p.C)[(long)m * p.ldc + (n[0] >> 1)] = f2bf(silu_f(y[0]) * y[1]);
-          ((bf16_t*)p.C)[(long)m * p.ldc + (n[2] >> 1)] = f2bf(silu_f(y[2]) * y[3]);
+          gemv_store_swiglu(p, m, n[0], y[0], y[1]);
+          gemv_store_swiglu(p, m, n[2], y[2], y[3]);
         }
-      } else {  // epi 3: the projection is rounded to 16 bits first (what the prefill GEMM stores), then rotate_half in f32
-        const int HHD = p.H * p.HD;
-        const int sect = e_lo / HHD, nn = e_lo - sect * HHD;
-        const int hh = nn / p.HD;
-        const int HALF = p.HD / 2;
-        int pos = 0;
-        long bh = 0;
-        if (ok) {
-          pos = p.pos_dev ? p.pos_dev[m * p.pos_stride] : p.pos0;
-          bh = (long)m * p.H + hh;
-        }
+      } else {  // epi 3
+        int sect, hh;
+        gemv_qkv_head(p, e_lo, sect, hh);
+        const int pos = ok ? gemv_pos(p, m) : 0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int d = n[r] - sect * HHD - hh * p.HD;
-          const float a = bf2f(f2bf(y[r]));
-          const float partner = __shfl_xor(a, 32, 64);  // row rr <-> rr +- 8 = d <-> d +- HD/2: two fg steps = 32 lanes away
-          if (ok) {
-            if (sect == 2) {
-              if constexpr (PAGED) p.vt[gf_vt_page_off(p, m, hh, pos, d)] = f2bf(y[r]);
-              else p.vt[(bh * p.HD + d) * p.kv_stride + pos] = f2bf(y[r]);
-            } else {
-              float o = a;
-              if (p.cosT) {
-                const int dc = d < HALF ? d : d - HALF;
-                const float sgn = d < HALF ? -1.f : 1.f;
-                o = a * p.cosT[(long)pos * HALF + dc] + sgn * partner * p.sinT[(long)pos * HALF + dc];
-              }
-              if (sect == 0) p.q[bh * p.HD + d] = f2bf(o);
-              else if constexpr (PAGED) p.kc[gf_k_page_off(p, m, hh, pos, d)] = f2bf(o);
-              else p.kc[(bh * p.kv_stride + pos) * p.HD + d] = f2bf(o);
-            }
-          }
+          const float partner = __shfl_xor(bf2f(f2bf(y[r])), 32, 64);  // row rr <-> rr +- 8 = d <-> d +- HD/2: two fg steps = 32 lanes away
+          if (ok) gemv_store_qkv<PAGED>(p, m, pos, sect, hh, n[r], y[r], partner);
         }
       }
     }
@@ -384,15 +333,10 @@ int gr_launch_gemv_fp8(const GemvFArgs& p, int MB, int n_cu, hipStream_t stream)
   size_t lds = (size_t)MB * (p.K + 16);
   if (p.x_mode == 2) lds += (size_t)MB * p.K * sizeof(bf16_t);  // the merged context before it is quantised
   if (lds > 128 * 1024 || (p.x_mode != 1 && p.K > 12288)) return GR_EINVAL;  // (the row quantiser holds 6 chunks of 8 per thread and row)
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemv_fp8_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemv_fp8_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemv_fp8_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemv_fp8_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-      return GR_EINVAL;
-    attr_set = true;
-  }
+  static void (*const kernels[2][2])(GemvFArgs) = {{gemv_fp8_kernel<4>, gemv_fp8_kernel<8>}, {gemv_fp8_kernel<4, true>, gemv_fp8_kernel<8, true>}};
+  for (const auto& row : kernels)
+    for (auto k : row)
+      if (gr_set_max_lds((const void*)k, 128 * 1024) != hipSuccess) return GR_EINVAL;
   const int groups = p.N / G8_ROWS;
   // persistent over row groups, every workgroup the same number of them (+-1): 768 groups on 512 slots would leave half the
   // workgroups a second group to run alone (round 6: grid = groups / rounds instead of the slot count; gate/up 29.0 -> 26.2 us, head
@@ -403,10 +347,6 @@ int gr_launch_gemv_fp8(const GemvFArgs& p, int MB, int n_cu, hipStream_t stream)
   const int cap = G8_WG_PER_CU * n_cu, rounds = (groups + cap - 1) / cap;
   const dim3 grid((groups + rounds - 1) / rounds);
 #endif
-  if (p.table) {
-    if (MB == 4) hipLaunchKernelGGL((gemv_fp8_kernel<4, true>), grid, dim3(256), lds, stream, p);
-    else hipLaunchKernelGGL((gemv_fp8_kernel<8, true>), grid, dim3(256), lds, stream, p);
-  } else if (MB == 4) hipLaunchKernelGGL(gemv_fp8_kernel<4>, grid, dim3(256), lds, stream, p);
-  else hipLaunchKernelGGL(gemv_fp8_kernel<8>, grid, dim3(256), lds, stream, p);
+  hipLaunchKernelGGL(kernels[p.table != nullptr][MB == 8], grid, dim3(256), lds, stream, p);  // [paged][8 batch rows]
   return GR_OK;
 }

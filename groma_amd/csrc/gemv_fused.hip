@@ -54,23 +54,14 @@ __global__ __launch_bounds__(256, (XG && MB == 8) ? 1 : 2) void gemv_fused_kerne
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ngroups = (p.N + ROWS - 1) / ROWS;
 
-  // ---- a group's rows.  epi 3 (fused QKV): inside the q and k sections a group takes ROWS/2 dims d and their rotate_half
-  // partners d + HD/2 of one head; the v section and every other mode take ROWS consecutive rows.
-  // (row numbers and row bases are wave-uniform scalars: the loads below must issue back to back)
-  // The two halves are runs of ROWS/2 consecutive rows: two scalar bases + r * ldw in the per-lane offset (N % ROWS == 0 is
+  // ---- a group's rows (gemv_group_rows).  Row numbers and row bases are wave-uniform scalars: the loads below must issue back to
+  // back.  The two halves are runs of ROWS/2 consecutive rows: two scalar bases + r * ldw in the per-lane offset (N % ROWS == 0 is
   // checked by the entry point, so no row is ever clamped).
   int r_lo, r_hi;                // first row of the lower / upper half of the current group's rows
   const char *base_lo, *base_hi; // their addresses (SGPR pairs)
   const unsigned ldwB = (unsigned)p.ldw * 2u;
   auto set_group = [&](int g) {
-    r_lo = g * ROWS;
-    r_hi = g * ROWS + ROWS / 2;
-    if (p.epi == 3 && (long)g * ROWS < 2L * p.H * p.HD) {
-      const int bph = p.HD / ROWS;  // groups per head
-      const int hh = g / bph, j = g - hh * bph;
-      r_lo = hh * p.HD + j * (ROWS / 2);
-      r_hi = r_lo + p.HD / 2;
-    }
+    gemv_group_rows<ROWS>(p, g, r_lo, r_hi);
     base_lo = (const char*)(p.W + (long)r_lo * p.ldw);
     base_hi = (const char*)(p.W + (long)r_hi * p.ldw);
   };
@@ -210,29 +201,10 @@ __global__ __launch_bounds__(256, (XG && MB == 8) ? 1 : 2) void gemv_fused_kerne
     __syncthreads();
   } else if (!XG && p.x_mode == 2) {  // merge the key slices of decode_attention (slice order; rounded like its nsplit = 1 output)
     first_slices();
-    const int hd = p.a_hd, c8 = p.K >> 3;
+    const int c8 = p.K >> 3;
     for (int idx = tid; idx < MB * c8; idx += 256) {
       const int m = idx / c8, k0 = (idx - m * c8) << 3;
-      union { bf16x8 v; uint32_t u[4]; } pk;
-      pk.v = zero8;
-      if (m < p.M) {
-        const int hh = k0 / hd, dd = k0 - hh * hd;
-        const float* base = p.a_parts + ((long)(m * (p.K / hd) + hh) * p.a_nsplit) * (hd + 2);
-        float mx = -1e30f;
-        for (int i = 0; i < p.a_nsplit; ++i) mx = fmaxf(mx, base[i * (hd + 2) + hd]);
-        float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, l = 0.f;
-        for (int i = 0; i < p.a_nsplit; ++i) {
-          const float* bi = base + i * (hd + 2);
-          const float f = __expf(bi[hd] - mx);
-          l += f * bi[hd + 1];
-          const f32x4 o0 = *(const f32x4*)(bi + dd), o1 = *(const f32x4*)(bi + dd + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { o[e] += f * o0[e]; o[4 + e] += f * o1[e]; }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pk.u[e] = pack2bf(o[2 * e] / l, o[2 * e + 1] / l);
-      }
-      *(bf16x8*)(xs + (long)m * p.K + k0) = pk.v;
+      *(bf16x8*)(xs + (long)m * p.K + k0) = gemv_merge8(p, m, k0);
     }
     __syncthreads();
   } else {
@@ -326,40 +298,17 @@ __global__ __launch_bounds__(256, (XG && MB == 8) ? 1 : 2) void gemv_fused_kerne
       const int n = rr < ROWS / 2 ? e_lo + rr : e_hi + (rr - ROWS / 2);
       const bool ok = lane < NV && m < p.M;
       if (p.epi == 0) {
-        if (ok) ((float*)p.C)[(long)m * p.ldc + n] = val;
+        if (ok) gemv_store_f32(p, m, n, val);
       } else if (p.epi == 1) {
-        if (ok) p.resid[(long)m * p.ldr + n] += val;
-      } else if (p.epi == 2) {  // interleaved rows: even = gate_j, odd = up_j ; partner row = lane ^ MB
+        if (ok) gemv_add_resid(p, m, n, val);
+      } else if (p.epi == 2) {  // partner row = lane ^ MB
         const float other = __shfl_xor(val, MB, 64);
-        if (ok && (rr & 1) == 0) ((bf16_t*)p.C)[(long)m * p.ldc + (n >> 1)] = f2bf(silu_f(val) * other);
-      } else {  // epi 3: the summed projection is rounded to 16 bits first (what the prefill GEMM stores), then rotate_half in f32
-        // all rows of a group lie in ONE head (HD % ROWS == 0): section, head and the first dim come from the group's first row --
-        // wave-uniform scalars, no per-lane division
-        const int HHD = p.H * p.HD;
-        const int sect = e_lo / HHD, nn = e_lo - sect * HHD;
-        const int hh = nn / p.HD;
-        const int d = (rr < ROWS / 2 ? e_lo + rr : e_hi + (rr - ROWS / 2)) - sect * HHD - hh * p.HD;
-        const int HALF = p.HD / 2;
-        const float a = bf2f(f2bf(val));
-        const float partner = __shfl_xor(a, (ROWS / 2) * MB, 64);  // row r <-> r + ROWS/2 = d <-> d + HD/2 (q / k sections)
-        if (ok) {
-          const int pos = p.pos_dev ? p.pos_dev[m * p.pos_stride] : p.pos0;
-          const long bh = (long)m * p.H + hh;
-          if (sect == 2) {
-            if constexpr (PAGED) p.vt[gf_vt_page_off(p, m, hh, pos, d)] = f2bf(val);
-            else p.vt[(bh * p.HD + d) * p.kv_stride + pos] = f2bf(val);
-          } else {
-            float o = a;
-            if (p.cosT) {
-              const int dc = d < HALF ? d : d - HALF;
-              const float sgn = d < HALF ? -1.f : 1.f;
-              o = a * p.cosT[(long)pos * HALF + dc] + sgn * partner * p.sinT[(long)pos * HALF + dc];
-            }
-            if (sect == 0) p.q[bh * p.HD + d] = f2bf(o);
-            else if constexpr (PAGED) p.kc[gf_k_page_off(p, m, hh, pos, d)] = f2bf(o);
-            else p.kc[(bh * p.kv_stride + pos) * p.HD + d] = f2bf(o);
-          }
-        }
+        if (ok && (rr & 1) == 0) gemv_store_swiglu(p, m, n, val, other);
+      } else {  // epi 3
+        int sect, hh;
+        gemv_qkv_head(p, e_lo, sect, hh);
+        const float partner = __shfl_xor(bf2f(f2bf(val)), (ROWS / 2) * MB, 64);  // row r <-> r + ROWS/2 = d <-> d + HD/2 (q / k sections)
+        if (ok) gemv_store_qkv<PAGED>(p, m, gemv_pos(p, m), sect, hh, n, val, partner);
       }
     }
     if (nxt >= ngroups) break;
@@ -373,7 +322,7 @@ __global__ __launch_bounds__(256, (XG && MB == 8) ? 1 : 2) void gemv_fused_kerne
 int gr_prof_begin(hipStream_t stream, int M, int N, int K, int tag);
 void gr_prof_end(hipStream_t stream, int idx);
 
-// table != null: gr_gemv_fused_paged (epi 3 into the paged cache); kv_stride is then the row capacity table_ld * 64
+// table != null: gr_gemv_fused_paged (epi 3 into the paged cache); kv_stride is then the row capacity table_ld * KV_PAGE
 static int gemv_fused_launch(const gr_gemv_desc* d, const int* table, int table_ld, hipStream_t stream) {
   if (GR_SP) return GR_EINVAL;  // no split-operand form: a decode step of the reference-precision build runs the general kernels
   if (!d || !d->W || d->M <= 0 || d->M > 8 || d->N <= 0 || d->K <= 0 || d->K % 64 != 0 || d->ldw < d->K) return GR_EINVAL;
@@ -404,22 +353,16 @@ static int gemv_fused_launch(const gr_gemv_desc* d, const int* table, int table_
   p.H = d->H; p.HD = d->HD; p.pos0 = d->pos0; p.kv_stride = d->kv_stride; p.pos_dev = d->pos_dev; p.pos_stride = d->pos_stride;
   p.w_scale = d->w_scale;
   p.table = table; p.table_ld = table_ld;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemv_fused_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemv_fused_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemv_fused_kernel<4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemv_fused_kernel<8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-      return GR_EINVAL;
-    attr_set = true;
-  }
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return GR_EINVAL;
-    n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
+  // [paged][x_mode 0][8 batch rows]
+  static void (*const kernels[2][2][2])(GemvFArgs) = {
+      {{gemv_fused_kernel<4, false>, gemv_fused_kernel<8, false>}, {gemv_fused_kernel<4, true>, gemv_fused_kernel<8, true>}},
+      {{gemv_fused_kernel<4, false, true>, gemv_fused_kernel<8, false, true>}, {gemv_fused_kernel<4, true, true>, gemv_fused_kernel<8, true, true>}}};
+  for (const auto& paged : kernels)
+    for (auto k : paged[0])  // the instantiations that stage x in LDS
+      if (gr_set_max_lds((const void*)k, 128 * 1024) != hipSuccess) return GR_EINVAL;
+  const int cus = gr_cu_count();
+  if (cus < 0) return GR_EINVAL;
+  const int n_cu = cus > 0 ? cus : 256;
   const int groups = gr_cdiv(d->N, ROWS);
   // persistent over row groups.  (An even split -- grid = groups / rounds -- was measured in round 6: the e4m3 stream gains from it,
   // gemv_fp8.hip; here gate/up loses 35.5 -> 38.1 us at 4 rows, profiles/r06_gemv_grid.txt.)
@@ -434,21 +377,7 @@ static int gemv_fused_launch(const gr_gemv_desc* d, const int* table, int table_
     return GR_OK;
   }
   const int prof = gr_prof_begin(stream, d->M, d->N, d->K, 8 | 32);
-  if (table) {
-    if (d->x_mode == 0) {
-      if (MB == 4) hipLaunchKernelGGL((gemv_fused_kernel<4, true, true>), grid, dim3(256), 0, stream, p);
-      else hipLaunchKernelGGL((gemv_fused_kernel<8, true, true>), grid, dim3(256), 0, stream, p);
-    } else {
-      if (MB == 4) hipLaunchKernelGGL((gemv_fused_kernel<4, false, true>), grid, dim3(256), lds, stream, p);
-      else hipLaunchKernelGGL((gemv_fused_kernel<8, false, true>), grid, dim3(256), lds, stream, p);
-    }
-  } else if (d->x_mode == 0) {
-    if (MB == 4) hipLaunchKernelGGL((gemv_fused_kernel<4, true>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((gemv_fused_kernel<8, true>), grid, dim3(256), 0, stream, p);
-  } else {
-    if (MB == 4) hipLaunchKernelGGL((gemv_fused_kernel<4, false>), grid, dim3(256), lds, stream, p);
-    else hipLaunchKernelGGL((gemv_fused_kernel<8, false>), grid, dim3(256), lds, stream, p);
-  }
+  hipLaunchKernelGGL(kernels[table != nullptr][d->x_mode == 0][MB == 8], grid, dim3(256), lds, stream, p);  // (lds = 0 at x_mode 0)
   gr_prof_end(stream, prof);
   GR_CHECK_LAUNCH();
   return GR_OK;
@@ -456,12 +385,12 @@ static int gemv_fused_launch(const gr_gemv_desc* d, const int* table, int table_
 
 extern "C" int gr_gemv_fused(const gr_gemv_desc* d, hipStream_t stream) { return gemv_fused_launch(d, nullptr, 0, stream); }
 
-// The QKV stream (epi 3) writing K and V^T into a paged cache: d->kc [pages, H, 64, HD], d->vt [pages, H, HD, 64]; row m's position pos
-// lands in page block_table[m * table_ld + pos / 64] (table_ld <= 128).  d->kv_stride is ignored (the row capacity is table_ld * 64).
+// The QKV stream (epi 3) writing K and V^T into a paged cache (kv_layout.h: d->kc and d->vt are the page pools, block_table row m is
+// batch row m's table, table_ld <= 128).  d->kv_stride is ignored (the row capacity is table_ld * KV_PAGE).
 extern "C" int gr_gemv_fused_paged(const gr_gemv_desc* d, const int* block_table, int table_ld, hipStream_t stream) {
   if (GR_SP) return GR_EINVAL;
   if (!d || !block_table || d->epi != 3 || table_ld <= 0 || table_ld > 128) return GR_EINVAL;
   gr_gemv_desc e = *d;
-  e.kv_stride = table_ld * 64;
+  e.kv_stride = table_ld * KV_PAGE;
   return gemv_fused_launch(&e, block_table, table_ld, stream);
 }

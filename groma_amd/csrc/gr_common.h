@@ -4,6 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
+#include <mutex>
+#include <set>
+#include <utility>
+
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
@@ -245,6 +250,35 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 }
 
 static inline int gr_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- launcher state that belongs to a DEVICE, not to the process: a process may drive several, from several threads.
+// Raise kernel `fn`'s dynamic-LDS limit to `bytes` on the current device, once per (kernel, device); the runtime's error if it refuses.
+inline hipError_t gr_set_max_lds(const void* fn, int bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> done;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lock(mu);
+  if (done.count({fn, dev})) return hipSuccess;
+  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.insert({fn, dev});
+  return e;
+}
+// CUs of the current device (-1 if the runtime cannot tell), queried once per device
+inline int gr_cu_count() {
+  static std::mutex mu;
+  static std::map<int, int> cus;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return -1;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cus.find(dev);
+  if (it != cus.end()) return it->second;
+  int n = 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
+  cus[dev] = n;
+  return n;
+}
 
 #define GR_CHECK_LAUNCH()                      \
   do {                                         \

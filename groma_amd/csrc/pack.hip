@@ -1,6 +1,7 @@
 // Layout / packing kernels around the GEMMs (all HBM-bound, 16-B vector accesses).
 // Each cites the reference statement whose data movement it performs.
 #include "gr_common.h"
+#include "kv_layout.h"
 #include "../../include/groma_hip.h"
 
 // ---------------------------------------------------------------------------------------
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
       if (which == 0 && !q) continue;
       const long sp = src + (long)which * H * HD;
       bf16_t* dst = which == 0 ? q : k;
-      const long di = which == 0 ? (((long)b * H + h) * L + t) * HD : (((long)b * H + h) * kv_stride + pos) * HD;
+      const long di = which == 0 ? (((long)b * H + h) * L + t) * HD : kv_k_slot((long)b * H + h, pos, 0, HD, kv_stride);
       float x[8];
       ld8f(qkv, sp + d, x);
       if (cosT) {
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
     const int d = it >> 3, seg = it & 7;
     const int tb = t0 + seg * 8;
     if (tb >= L) continue;
-    const long di = (((long)b * H + h) * HD + d) * kv_stride + pos0 + tb;
+    const long di = kv_vt_slot((long)b * H + h, pos0 + tb, d, HD, kv_stride);
     if (aligned && tb + 8 <= L) {
       float o[8];
 #pragma unroll
@@ -85,8 +86,8 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
   }
 }
 #else
-// PAGED (gr_qkv_split_paged, L = 1): k is a pool [pages, H, 64, HD], vt a pool [pages, H, HD, 64]; row b's position pos is in page
-// table[b * table_ld + pos / 64] (page 0, the sink page, past the end of the table).  The values are the slot form's, bit for bit.
+// PAGED (gr_qkv_split_paged, L = 1): k and vt are the page pools of kv_layout.h, table row b is batch row b's block table.  The values
+// are the slot form's, bit for bit.
 template <int HD, bool PAGED = false>
 __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ q,
                                                         bf16_t* __restrict__ k, bf16_t* __restrict__ vt,
@@ -99,10 +100,6 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
   const int h = blockIdx.y, b = blockIdx.z;
   // device-resident write position (graph-captured / ragged decode): row b appends at pos_dev[b * pos_stride]
   const int pos0 = pos_dev ? pos_dev[b * pos_stride] : pos0_arg;
-  auto page = [&](int pos) -> long {
-    const int i = pos >> 6;
-    return (unsigned)i < (unsigned)table_ld ? (long)table[(long)b * table_ld + i] : 0L;
-  };
   const int tid = threadIdx.x;
   const long row_stride = 3L * H * HD;
   constexpr int HALF = HD / 2;
@@ -123,8 +120,8 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
       const bf16_t* sp = src + (long)which * H * HD;
       if (which == 0 && !q) continue;  // q stays in the fused buffer: gr_attention_bf16 reads (and rotates) it there
       bf16_t* dst;
-      if constexpr (PAGED) dst = which == 0 ? q + (((long)b * H + h) * L + t) * HD : k + ((page(pos) * H + h) * 64 + (pos & 63)) * HD;
-      else dst = which == 0 ? q + (((long)b * H + h) * L + t) * HD : k + (((long)b * H + h) * kv_stride + pos) * HD;
+      if constexpr (PAGED) dst = which == 0 ? q + (((long)b * H + h) * L + t) * HD : k + kv_k_paged(kv_page(table, table_ld, b, pos), H, h, pos, 0, HD);
+      else dst = which == 0 ? q + (((long)b * H + h) * L + t) * HD : k + kv_k_slot((long)b * H + h, pos, 0, HD, kv_stride);
       const bf16x8 x = *(const bf16x8*)(sp + d);
       if (cosT) {
         const int dp = d < HALF ? d + HALF : d - HALF;  // rotate_half partner
@@ -156,8 +153,8 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
     const int tb = t0 + seg * 8;
     if (tb >= L) continue;
     bf16_t* dst;  // (PAGED: L = 1, so the one column written lies in pos0's page)
-    if constexpr (PAGED) dst = vt + ((page(pos0 + tb) * H + h) * HD + d) * 64 + ((pos0 + tb) & 63);
-    else dst = vt + (((long)b * H + h) * HD + d) * kv_stride + pos0 + tb;
+    if constexpr (PAGED) dst = vt + kv_vt_paged(kv_page(table, table_ld, b, pos0 + tb), H, h, pos0 + tb, d, HD);
+    else dst = vt + kv_vt_slot((long)b * H + h, pos0 + tb, d, HD, kv_stride);
     if (aligned && tb + 8 <= L) {
       union { bf16x8 v; bf16_t e[8]; } o;
 #pragma unroll
@@ -197,15 +194,15 @@ extern "C" int gr_qkv_split(const void* qkv, void* q, void* k, void* vt, const f
   return GR_OK;
 }
 
-// The decode step's RoPE + K / V^T write (L = 1) into a paged cache: k_pool [pages, H, 64, hd], vt_pool [pages, H, hd, 64], row b's
-// position in page block_table[b * table_ld + pos / 64].  No split-operand form.
+// The decode step's RoPE + K / V^T write (L = 1) into a paged cache (kv_layout.h: k_pool and vt_pool are the page pools, block_table
+// row b is batch row b's table).  No split-operand form.
 extern "C" int gr_qkv_split_paged(const void* qkv, void* q, void* k_pool, void* vt_pool, const float* cosT, const float* sinT, int B,
                                   int H, int L, int head_dim, int pos0, const int* block_table, int table_ld, const int* pos_dev,
                                   int pos_stride, hipStream_t stream) {
   if (GR_SP) return GR_EINVAL;
   if (!qkv || !k_pool || !vt_pool || !block_table || B <= 0 || H <= 0 || L != 1) return GR_EINVAL;
   if ((cosT == nullptr) != (sinT == nullptr) || table_ld <= 0 || table_ld > 128) return GR_EINVAL;
-  if (!pos_dev && (pos0 < 0 || pos0 >= table_ld * 64)) return GR_EINVAL;
+  if (!pos_dev && (pos0 < 0 || pos0 >= table_ld * KV_PAGE)) return GR_EINVAL;
 #if !GR_SP
   dim3 grid(1, H, B);
   if (head_dim == 128)
@@ -223,8 +220,8 @@ extern "C" int gr_qkv_split_paged(const void* qkv, void* q, void* k_pool, void* 
 // ---------------------------------------------------------------------------------------
 // Staged prefill rows -> their pages (the continuous batcher's admission into a paged cache).  k_src [n_src, H, S, hd] and
 // vt_src [n_src, H, hd, S] are the staging cache; entry i moves staging row src_rows[i] into the pages of table row dst_rows[i]
-// (< n_dst): every whole 64-position page below lens[i] (clamped to max_len).  One block per (page, head, entry); 16-B copies
-// (a K page of a head is one contiguous 64 x hd run on both sides, a V^T page hd runs of 64).
+// (< n_dst): every page below lens[i] (clamped to max_len).  One block per (page, head, entry); 16-B copies (a K page of a head is
+// one contiguous KV_PAGE x hd run on both sides, a V^T page hd runs of KV_PAGE).
 template <int HD>
 __global__ __launch_bounds__(256) void kv_scatter_pages_kernel(const bf16_t* __restrict__ ks, const bf16_t* __restrict__ vs,
                                                                bf16_t* __restrict__ kp, bf16_t* __restrict__ vp,
@@ -235,14 +232,17 @@ __global__ __launch_bounds__(256) void kv_scatter_pages_kernel(const bf16_t* __r
   const int j = blockIdx.x, h = blockIdx.y, i = blockIdx.z;
   const int sr = src_rows[i], dr = dst_rows[i];
   const int len = min(lens[i], max_len);
-  if (sr < 0 || sr >= n_src || dr < 0 || dr >= n_dst || j * 64 >= len) return;
+  if (sr < 0 || sr >= n_src || dr < 0 || dr >= n_dst || j * KV_PAGE >= len) return;
+  const int s0 = j * KV_PAGE;  // the page's first position
   const long pg = table[(long)dr * table_ld + j];
-  const bf16x8* ksrc = (const bf16x8*)(ks + (((long)sr * H + h) * S + j * 64) * HD);
-  bf16x8* kdst = (bf16x8*)(kp + (pg * H + h) * 64 * HD);
-  for (int c = threadIdx.x; c < 64 * HD / 8; c += 256) kdst[c] = ksrc[c];
-  for (int c = threadIdx.x; c < HD * 8; c += 256) {
-    const int d = c >> 3, e = c & 7;
-    *(bf16x8*)(vp + ((pg * H + h) * HD + d) * 64 + e * 8) = *(const bf16x8*)(vs + (((long)sr * H + h) * HD + d) * S + j * 64 + e * 8);
+  const long sh = (long)sr * H + h;
+  const bf16x8* ksrc = (const bf16x8*)(ks + kv_k_slot(sh, s0, 0, HD, S));
+  bf16x8* kdst = (bf16x8*)(kp + kv_k_paged(pg, H, h, 0, 0, HD));
+  for (int c = threadIdx.x; c < KV_PAGE * HD / 8; c += 256) kdst[c] = ksrc[c];
+  static_assert(KV_PAGE == 64, "a V^T page row is 8 chunks of 8 positions");
+  for (int c = threadIdx.x; c < HD * 8; c += 256) {  // (dim d, 8 positions from e)
+    const int d = c >> 3, e = (c & 7) * 8;
+    *(bf16x8*)(vp + kv_vt_paged(pg, H, h, e, d, HD)) = *(const bf16x8*)(vs + kv_vt_slot(sh, s0, d, HD, S) + e);
   }
 }
 
@@ -251,9 +251,9 @@ extern "C" int gr_kv_scatter_pages(const void* k_src, const void* vt_src, void* 
                                    int n_dst, int H, int S, int head_dim, int max_len, hipStream_t stream) {
   if (GR_SP) return GR_EINVAL;
   if (!k_src || !vt_src || !k_pool || !vt_pool || !block_table || !src_rows || !dst_rows || !lens) return GR_EINVAL;
-  if (n <= 0 || n_src <= 0 || n_dst <= 0 || H <= 0 || S <= 0 || S % 64 != 0 || table_ld <= 0 || table_ld > 128) return GR_EINVAL;
-  if (max_len <= 0 || max_len > S || max_len > table_ld * 64) return GR_EINVAL;
-  dim3 grid(gr_cdiv(max_len, 64), H, n);
+  if (n <= 0 || n_src <= 0 || n_dst <= 0 || H <= 0 || S <= 0 || S % KV_PAGE != 0 || table_ld <= 0 || table_ld > 128) return GR_EINVAL;
+  if (max_len <= 0 || max_len > S || max_len > table_ld * KV_PAGE) return GR_EINVAL;
+  dim3 grid(gr_cdiv(max_len, KV_PAGE), H, n);
   if (head_dim == 128)
     hipLaunchKernelGGL(kv_scatter_pages_kernel<128>, grid, dim3(256), 0, stream, (const bf16_t*)k_src, (const bf16_t*)vt_src,
                        (bf16_t*)k_pool, (bf16_t*)vt_pool, block_table, table_ld, src_rows, dst_rows, lens, n_src, n_dst, H, S, max_len);
