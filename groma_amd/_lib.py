@@ -75,6 +75,8 @@ SIGNATURES = {
     "gr_decode_attention_paged": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _F, _P, _I, _I, _P, _P],
     "gr_qkv_split_paged": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P],
     "gr_kv_scatter_pages": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "gr_kv_append_paged": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P],
+    "gr_attention_paged": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _F, _P, _I, _L, _P, _P, _P],
     "gr_resize_h_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "gr_resize_v_norm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "gr_cv2_resize_norm": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "gr_common.h"
+#include "kv_layout.h"
 #include "../../include/groma_hip.h"
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -40,6 +41,8 @@ struct AttnArgs {
   int B, H, Lq, Skv, kv_stride;
   int causal, q_pos0;
   float scale_log2;  // softmax scale * log2(e)
+  const int* table;  // PAGED: block table (kv_layout.h), row b at table + b * table_ld; k / vt are the page pools
+  int table_ld;
 };
 
 #ifdef G256_CLK  // diagnostic build (tests/diag/build_clk.py): per-iteration segment clocks of block 0 / wave 0
@@ -132,7 +135,10 @@ __device__ __forceinline__ void att_static_for(F&& f) {
   }
 }
 
-template <int HD>
+// PAGED (gr_attention_paged): k and vt are the page pools of kv_layout.h.  A key tile is 64 keys = exactly one page, so only the
+// global base of each tile's K / V^T DMA changes (the page id is read once per tile, wave-uniform); LDS images, MFMA loop and
+// soft-max are the slot form's, and so are the bits.
+template <int HD, bool PAGED = false>
 __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs p) {
   constexpr int KV = 64;
   constexpr int QT = 2;               // 16-row query tiles per wave -> 32 query rows / wave, 128 / block
@@ -194,10 +200,13 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
   const int wav_first = min(q0 + wave * (16 * QT), p.Lq - 1);
   const int wav_min_limit = p.causal ? min(kvmax, q_pos0 + wav_first + 1) : kvmax;  // min over the wave's rows
 
+  // PAGED: the page that holds key tile kv0 of this row (wave-uniform; past the row's table: the sink page)
+  auto tile_page = [&](int kv0) -> long { return __builtin_amdgcn_readfirstlane((int)kv_page(p.table, p.table_ld, b, kv0)); };
   // stage K tile (lds chunk position pos holds logical chunk pos ^ (row&7)) and Vt tile of kv tile t into buffer t&1
   auto stage_k = [&](int t) {
     const int kv0 = t * KV;
     char* ksm = smem + (t & 1) * STAGE;
+    const long pg = PAGED ? tile_page(kv0) : 0;
     constexpr int NCH = KV * KCH;
 #pragma unroll
     for (int i = 0; i < NCH / 256; ++i) {
@@ -205,21 +214,27 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
       const int row = q / KCH, pos = q % KCH;
       const int c = pos ^ kswz(row);
       int kr = kv0 + row;
-      if (kr > Skv - 1) kr = Skv - 1;
-      __builtin_amdgcn_global_load_lds((gptr_t)(Kp + (long)kr * (HD * SPW) + c * 8), (lptr_t)(ksm + i * 4096 + wave * 1024), 16, 0, 0);
+      if (kr > Skv - 1) kr = Skv - 1;  // (kv0 <= Skv - 1: the clamped row stays in the tile's page)
+      const bf16_t* src;
+      if constexpr (PAGED) src = p.k + kv_k_paged(pg, p.H, h, kr, c * 8, HD);
+      else src = Kp + (long)kr * (HD * SPW) + c * 8;
+      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(ksm + i * 4096 + wave * 1024), 16, 0, 0);
     }
   };
   auto stage_v = [&](int t) {
     const int kv0 = t * KV;
     char* vsm = smem + (t & 1) * STAGE + KTILE;
+    const long pg = PAGED ? tile_page(kv0) : 0;
     constexpr int NVC = HD * VCH;
 #pragma unroll
     for (int i = 0; i < NVC / 256; ++i) {
       const int q = i * 256 + tid;
       const int row = q / VCH, pos = q % VCH;
       const int c = pos ^ (row & VSWZ);
-      __builtin_amdgcn_global_load_lds((gptr_t)(Vp + ((long)row * p.kv_stride + kv0) * SPW + c * 8),
-                                       (lptr_t)(vsm + i * 4096 + wave * 1024), 16, 0, 0);
+      const bf16_t* src;
+      if constexpr (PAGED) src = p.vt + kv_vt_paged(pg, p.H, h, kv0, row, HD) + c * 8;
+      else src = Vp + ((long)row * p.kv_stride + kv0) * SPW + c * 8;
+      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(vsm + i * 4096 + wave * 1024), 16, 0, 0);
     }
   };
   auto stage = [&](int t) {
@@ -674,6 +689,7 @@ extern "C" int gr_attention_bf16(const void* q, const void* k, const void* vt, v
   p.B = B; p.H = H; p.Lq = Lq; p.Skv = Skv; p.kv_stride = kv_stride;
   p.causal = causal; p.q_pos0 = q_pos0;
   p.scale_log2 = scale * 1.44269504088896340736f;
+  p.table = nullptr; p.table_ld = 0;
   dim3 grid(B * H, gr_cdiv(Lq, 128));
   if (gr_set_max_lds((const void*)attention_kernel<128>, 65536 * GR_SPW) != hipSuccess ||
       gr_set_max_lds((const void*)attention_kernel<64>, 32768 * GR_SPW) != hipSuccess)
@@ -682,5 +698,40 @@ extern "C" int gr_attention_bf16(const void* q, const void* k, const void* vt, v
   else if (head_dim == 64) hipLaunchKernelGGL(attention_kernel<64>, grid, dim3(256), 32768 * GR_SPW, stream, p);
   else return GR_EINVAL;
   GR_CHECK_LAUNCH();
+  return GR_OK;
+}
+
+// Paged form (kv_layout.h): causal attention of Lq new positions per row over a paged cache -- the suffix prefill of the continuous
+// batcher's prefix cache.  Row b's queries sit at q_pos0_b + i (q_pos0_b = pos_dev ? pos_dev[b * pos_stride] : q_pos0) and see keys
+// 0 .. q_pos0_b + i (and < kv_len[b]), key s in page block_table[b * table_ld + s / 64].  Same bits as gr_attention_bf16 over a slot
+// cache holding the same keys.  No split-operand form.
+extern "C" int gr_attention_paged(const void* q, const void* k_pool, const void* vt_pool, void* out, const int* kv_len, int B, int H,
+                                  int Lq, const int* block_table, int table_ld, int head_dim, int q_pos0, float scale,
+                                  const int* pos_dev, int pos_stride, long q_ld, const float* rope_cos, const float* rope_sin,
+                                  hipStream_t stream) {
+  if (GR_SP) return GR_EINVAL;
+  if (!q || !k_pool || !vt_pool || !out || !block_table || B <= 0 || H <= 0 || Lq <= 0) return GR_EINVAL;
+  if (table_ld <= 0 || table_ld * KV_PAGE > 8192 || (head_dim != 128 && head_dim != 64)) return GR_EINVAL;
+  if (!pos_dev && (q_pos0 < 0 || q_pos0 + Lq > table_ld * KV_PAGE)) return GR_EINVAL;
+  if (q_ld < 0 || (q_ld > 0 && (q_ld % 8 != 0 || q_ld < (long)H * head_dim)) || (rope_cos == nullptr) != (rope_sin == nullptr))
+    return GR_EINVAL;
+#if !GR_SP
+  AttnArgs p;
+  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k_pool; p.vt = (const bf16_t*)vt_pool; p.out = (bf16_t*)out;
+  p.kv_len = kv_len;
+  p.pos_dev = pos_dev; p.pos_stride = pos_stride;
+  p.q_ld = q_ld; p.rope_cos = rope_cos; p.rope_sin = rope_sin;
+  p.B = B; p.H = H; p.Lq = Lq; p.Skv = q_pos0 + Lq; p.kv_stride = KV_PAGE;
+  p.causal = 1; p.q_pos0 = q_pos0;
+  p.scale_log2 = scale * 1.44269504088896340736f;
+  p.table = block_table; p.table_ld = table_ld;
+  dim3 grid(B * H, gr_cdiv(Lq, 128));
+  if (gr_set_max_lds((const void*)attention_kernel<128, true>, 65536) != hipSuccess ||
+      gr_set_max_lds((const void*)attention_kernel<64, true>, 32768) != hipSuccess)
+    return GR_EINVAL;
+  if (head_dim == 128) hipLaunchKernelGGL((attention_kernel<128, true>), grid, dim3(256), 65536, stream, p);
+  else hipLaunchKernelGGL((attention_kernel<64, true>), grid, dim3(256), 32768, stream, p);
+  GR_CHECK_LAUNCH();
+#endif
   return GR_OK;
 }

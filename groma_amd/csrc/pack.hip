@@ -87,8 +87,9 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
 }
 #else
 // PAGED (gr_qkv_split_paged, L = 1): k and vt are the page pools of kv_layout.h, table row b is batch row b's block table.  The values
-// are the slot form's, bit for bit.
-template <int HD, bool PAGED = false>
+// are the slot form's, bit for bit.  APPEND (gr_kv_append_paged, PAGED with any L): a V^T write that is not one aligned 8-position
+// store looks up the page of every position (a run of L > 1 positions may cross a page boundary).
+template <int HD, bool PAGED = false, bool APPEND = false>
 __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ q,
                                                         bf16_t* __restrict__ k, bf16_t* __restrict__ vt,
                                                         const float* __restrict__ cosT, const float* __restrict__ sinT,
@@ -163,7 +164,10 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i)
-        if (tb + i < L) dst[i] = vs[seg * 8 + i][d];
+        if (tb + i < L) {
+          if constexpr (APPEND) vt[kv_vt_paged(kv_page(table, table_ld, b, pos0 + tb + i), H, h, pos0 + tb + i, d, HD)] = vs[seg * 8 + i][d];
+          else dst[i] = vs[seg * 8 + i][d];
+        }
     }
   }
 }
@@ -212,6 +216,31 @@ extern "C" int gr_qkv_split_paged(const void* qkv, void* q, void* k_pool, void* 
     hipLaunchKernelGGL((qkv_split_kernel<64, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k_pool,
                        (bf16_t*)vt_pool, cosT, sinT, B, H, 1, pos0, 64, pos_dev, pos_stride, block_table, table_ld);
   else return GR_EINVAL;
+  GR_CHECK_LAUNCH();
+#endif
+  return GR_OK;
+}
+
+// The K / V^T write of a multi-position prefill (L positions per row, rows of the fused QKV buffer [B*L, 3*H*hd]) into a paged cache:
+// row b's positions pos0_b + i (pos0_b = pos_dev ? pos_dev[b * pos_stride] : pos0) land in the pages of table row b, positions past
+// the table in the sink page.  q is not written (gr_attention_paged reads and rotates it in the fused buffer).  The values are
+// gr_qkv_split's, bit for bit.  No split-operand form.
+extern "C" int gr_kv_append_paged(const void* qkv, void* k_pool, void* vt_pool, const float* cosT, const float* sinT, int B, int H, int L,
+                                  int head_dim, int pos0, const int* block_table, int table_ld, const int* pos_dev, int pos_stride,
+                                  hipStream_t stream) {
+  if (GR_SP) return GR_EINVAL;
+  if (!qkv || !k_pool || !vt_pool || !block_table || B <= 0 || H <= 0 || L <= 0) return GR_EINVAL;
+  if ((cosT == nullptr) != (sinT == nullptr) || table_ld <= 0 || table_ld > 128) return GR_EINVAL;
+  if (!pos_dev && (pos0 < 0 || pos0 + L > table_ld * KV_PAGE)) return GR_EINVAL;
+  if (head_dim != 128 && head_dim != 64) return GR_EINVAL;
+#if !GR_SP
+  dim3 grid(gr_cdiv(L, 64), H, B);
+  if (head_dim == 128)
+    hipLaunchKernelGGL((qkv_split_kernel<128, true, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, nullptr, (bf16_t*)k_pool,
+                       (bf16_t*)vt_pool, cosT, sinT, B, H, L, pos0, KV_PAGE, pos_dev, pos_stride, block_table, table_ld);
+  else
+    hipLaunchKernelGGL((qkv_split_kernel<64, true, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, nullptr, (bf16_t*)k_pool,
+                       (bf16_t*)vt_pool, cosT, sinT, B, H, L, pos0, KV_PAGE, pos_dev, pos_stride, block_table, table_ld);
   GR_CHECK_LAUNCH();
 #endif
   return GR_OK;

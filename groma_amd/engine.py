@@ -863,6 +863,51 @@ class LlamaEngine:
         logits = ops.gemm(hn, w["head"], out_f32=True)
         return logits.view(bs, L, self.Vpad)[:, :, : self.V], hn
 
+    def prefill_paged(self, h, bs, Lq, cache, table, pos_dev, kv_len=None):
+        """Prefill continuation on a PagedKVCache (the continuous batcher's prefix-cache hits): h f32 [bs*Lq, T] holds the input rows
+        of positions pos_dev[b] + i of row b (consumed as the residual stream, updated in place).  Their K / V^T go into the pages of
+        `table` (int32 [>= bs, table_ld]: an admission table of the caller's, not the live table the captured decode step reads), and
+        each query attends to keys 0 .. its position through it -- pages mapped from other rows included.  kv_len (i32 [bs]): row b's
+        keys end there (right padding of ragged suffixes; what a padding position writes lands in a page the row owns or in the sink
+        page).  Returns the logits of every suffix row, f32 [bs, Lq, V].  Same GEMMs, norms and summation orders as forward()'s
+        prefill, so a row's logits are bitwise those of the same positions of a full prefill."""
+        w, ws, T, H, hd = self.w, self.ws, self.T, self.H, self.hd
+        M = bs * Lq
+        if not getattr(cache, "paged", False) or self.prec is not None or ops.SP() != 1:
+            raise ValueError("prefill_paged needs a PagedKVCache and a single-type 16-bit or e4m3 stack")
+        if Lq < 2 or M <= 8 or table.shape[0] < bs or pos_dev is None:
+            # (M <= 8 would put the 16-bit GEMMs on the decode-step weight stream: another summation order than a full prefill's)
+            raise ValueError("prefill_paged needs Lq >= 2, bs * Lq > 8 rows, a table row per batch row and device positions")
+        fp8 = w["fp8"]
+        x_b, qkv_b = ws.get("sfx_x", (M, T), H16()), ws.get("sfx_qkv", (M, 3 * T), H16())
+        ctx_b, y_b = ws.get("sfx_ctx", (M, T), H16()), ws.get("sfx_y", (M, self.I), H16())
+        n_sk = ops.plan_ws_elems(M, [(3 * T, T), (T, T), (2 * self.I, T), (T, self.I)])
+        skw = ws.get("sfx_splitk", (n_sk,), F32) if n_sk else None
+        q8 = {K_: (ws.get(f"sfx_q8_{K_}", (M, K_), ops.FP8), ws.get(f"sfx_s8_{K_}", (M,), F32)) for K_ in ((T, self.I) if fp8 else ())}
+
+        def lin(x_f32, gain, wt, **kw):
+            if fp8:
+                x8, sx = ops.norm_fp8(x_f32, gain, None, self.eps, True, out=q8[x_f32.shape[-1]])
+                return ops.gemm(x8, wt[0], a_scale=sx, w_scale=wt[1], **kw)
+            return ops.gemm(ops.rmsnorm(x_f32, gain, self.eps, out=x_b), wt[0], split_ws=skw, **kw)
+
+        def lin_bf16(x_bf16, wt, **kw):
+            if fp8:
+                x8, sx = ops.quant_rows_fp8(x_bf16, out=q8[x_bf16.shape[-1]])
+                return ops.gemm(x8, wt[0], a_scale=sx, w_scale=wt[1], **kw)
+            return ops.gemm(x_bf16, wt[0], split_ws=skw, **kw)
+
+        for i, Lw in enumerate(w["layers"]):
+            qkv = lin(h, Lw["n1"], Lw["wqkv"], out=qkv_b)
+            ops.kv_append_paged(qkv, cache.k[i], cache.vt[i], table, B=bs, H=H, L=Lq, hd=hd, cos=w["cos"], sin=w["sin"],
+                                pos_dev=pos_dev, pos_stride=1)
+            ctx = ops.attention_paged(qkv, cache.k[i], cache.vt[i], table, B=bs, H=H, Lq=Lq, hd=hd, kv_len=kv_len, out=ctx_b,
+                                      pos_dev=pos_dev, pos_stride=1, cos=w["cos"], sin=w["sin"], fused=True)
+            lin_bf16(ctx, Lw["wo"], resid=h, out=h, out_f32=True)
+            y = lin(h, Lw["n2"], Lw["wgu"], act=3, out=y_b)
+            lin_bf16(y, Lw["wd"], resid=h, out=h, out_f32=True)
+        return self._head(h, bs, Lq, x_b, True)[0]
+
     def decode_logits(self, bs):
         """the padded f32 [bs, Vpad] buffer every single-position step (either path) leaves its logits in: a dedicated tensor,
         so a captured decode graph and its sampler keep addressing the same memory"""

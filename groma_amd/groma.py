@@ -581,7 +581,7 @@ class GromaModel:
     def forward(self, input_ids=None, inputs_embeds=None, labels=None, attention_mask=None, images=None,
                 refer_boxes=None, ground_boxes=None, past_key_values=None, use_cache=False, output_attentions=False,
                 output_hidden_states=False, return_dict=False, _last_logits_only=False, _reserve=0, _cache=None,
-                _seeds=None):
+                _seeds=None, _keep_embeds=False):
         if not self._loaded:
             raise RuntimeError("GromaModel has no weights: use from_pretrained / from_state_dict / from_synthetic")
         if output_attentions:
@@ -701,7 +701,8 @@ class GromaModel:
                 aux["lengths"] = mask_h.sum(-1).tolist()  # expanded length of every row (right padding excluded)
                 aux["hidden4"] = hidden4  # the four ViT states the path consumed (arena views: valid until the next forward)
                 aux["input_ids"] = new_ids_h
-                if getattr(self, "capture_embeds", False):  # parity tests: the LLM stage's exact input (emb is consumed in place)
+                if _keep_embeds or getattr(self, "capture_embeds", False):  # the LLM stage's exact input (emb is consumed in place):
+                    # parity tests, and the serving prefix cache (the rows a later suffix prefill recomputes)
                     aux["inputs_embeds"] = emb.view(bs, L, -1).clone()
                 self._last_aux = aux
             else:

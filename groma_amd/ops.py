@@ -539,6 +539,42 @@ def qkv_split_paged(qkv, q, k_pool, vt_pool, table, *, B, H, hd, pos0=0, cos=Non
                                       table.shape[1], _p(pos_dev), pos_stride, _stream()), "gr_qkv_split_paged")
 
 
+def kv_append_paged(qkv, k_pool, vt_pool, table, *, B, H, L, hd, pos0=0, cos=None, sin=None, pos_dev=None, pos_stride=0):
+    """K / V^T of L new positions per row (qkv = the fused projection rows [B*L, 3*H*hd]) into a paged cache: row b's positions
+    pos0_b + i land in the pages of table row b (pos0_b = pos_dev[b * pos_stride], or pos0); q stays in qkv"""
+    lib = _lib.load()
+    _chk(qkv, H16(), "qkv"); _chk(k_pool, H16(), "k_pool"); _chk(vt_pool, H16(), "vt_pool"); _chk(table, I32, "table")
+    if table.shape[0] < B:
+        raise ValueError("table has fewer rows than the batch")
+    if pos_dev is not None:
+        _chk(pos_dev, I32, "pos_dev")
+    _lib.check(lib.gr_kv_append_paged(_p(qkv), _p(k_pool), _p(vt_pool), _p(cos), _p(sin), B, H, L, hd, pos0, _p(table),
+                                      table.shape[1], _p(pos_dev), pos_stride, _stream()), "gr_kv_append_paged")
+
+
+def attention_paged(q, k_pool, vt_pool, table, *, B, H, Lq, hd, q_pos0=0, kv_len=None, scale=None, out=None, pos_dev=None,
+                    pos_stride=0, cos=None, sin=None, fused=False):
+    """causal attention of Lq queries per row over a paged cache (pools and table as for decode_attention_paged): row b's queries
+    sit at q_pos0_b + i (q_pos0_b = pos_dev[b * pos_stride], or q_pos0).  q: [B,H,Lq,hd], or with fused=True the fused projection
+    rows [B*Lq, ld] (rotated in place with cos / sin).  Returns out [B*Lq, H*hd]."""
+    lib = _lib.load()
+    _chk(q, H16(), "q"); _chk(k_pool, H16(), "k_pool"); _chk(vt_pool, H16(), "vt_pool"); _chk(table, I32, "table")
+    if table.shape[0] < B:
+        raise ValueError("table has fewer rows than the batch")
+    q_ld = q.shape[-1] if fused else 0
+    if scale is None:
+        scale = hd ** -0.5
+    if out is None:
+        out = torch.empty((B * Lq, H * hd), dtype=H16(), device=q.device)
+    if kv_len is not None:
+        _chk(kv_len, I32, "kv_len")
+    if pos_dev is not None:
+        _chk(pos_dev, I32, "pos_dev")
+    _lib.check(lib.gr_attention_paged(_p(q), _p(k_pool), _p(vt_pool), _p(out), _p(kv_len), B, H, Lq, _p(table), table.shape[1], hd,
+                                      q_pos0, scale, _p(pos_dev), pos_stride, q_ld, _p(cos), _p(sin), _stream()), "gr_attention_paged")
+    return out
+
+
 def kv_scatter_pages(k_src, vt_src, k_pool, vt_pool, table, rows, max_len):
     """staging cache (k_src [n_src, H, S, hd], vt_src [n_src, H, hd, S]) -> pages: rows = int32 device tensor [3, n] of
     (staging row, table row, length); every whole 64-position page below min(length, max_len) is copied.  One layer per call."""

@@ -30,9 +30,15 @@ With `kv_pages=N` the arena is PAGED instead (engine.PagedKVCache): N pages of 6
 block table that maps each row's positions to pages.  A request reserves the pages of its context bound at admission, keeps those
 its prompt and new tokens can reach, and gives them back when it finishes, so a fixed budget holds more and longer rows than
 `max_rows` slots of `max_len` each.  Admission is FIFO and waits while the head request's pages are not free.
+
+With `prefix_cache=True` on top (PrefixCache), a cold prompt's whole pages stay behind as an entry keyed by its image, boxes, seed and
+precision.  A later request of the same key whose ids share the image prefix maps those pages below p0 (the last page boundary inside
+the shared part) and prefills only [p0, L) on the pool (LlamaEngine.prefill_paged): the same tokens as a cold admission, without the
+vision stages and the prefix prefill.  Nothing writes below p0, so shared pages never need a copy.
 """
+import hashlib
 import threading
-from collections import deque
+from collections import OrderedDict, deque
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -74,7 +80,8 @@ class SlotTable:
 
 class PagePool:
     """Page bookkeeping of a paged KV cache (host side, no device work): pages 1..n are handed out, page 0 -- the sink page every
-    unowned block-table entry points at -- never is."""
+    unowned block-table entry points at -- never is.  A page may have several holders (live rows and prefix-cache entries that map
+    it): retain() adds one, release() drops one and frees the page with its last."""
 
     def __init__(self, n):
         if n < 1:
@@ -82,6 +89,7 @@ class PagePool:
         self.n = n
         self._free = deque(range(1, n + 1))
         self._used = set()
+        self._ref = {}   # page -> holders (pages in use only)
         self.high_water = 0
 
     def reserve(self, k):
@@ -92,19 +100,152 @@ class PagePool:
             return None
         ids = [self._free.popleft() for _ in range(k)]
         self._used.update(ids)
+        self._ref.update((i, 1) for i in ids)
         self.high_water = max(self.high_water, len(self._used))
         return ids
 
+    def retain(self, ids):
+        """one more holder for each of `ids` (pages in use; an id listed twice gains two)"""
+        ids = list(ids)
+        if any(i not in self._used for i in ids):
+            raise ValueError(f"pages {ids} are not all in use")
+        for i in ids:
+            self._ref[i] += 1
+
     def release(self, ids):
+        """one holder fewer for each of `ids`; a page goes back to the free list with its last holder"""
         ids = list(ids)
         if len(set(ids)) != len(ids) or any(i not in self._used for i in ids):
             raise ValueError(f"pages {ids} are not all in use")
-        self._used.difference_update(ids)
-        self._free.extend(ids)
+        for i in ids:
+            self._ref[i] -= 1
+            if self._ref[i] == 0:
+                del self._ref[i]
+                self._used.discard(i)
+                self._free.append(i)
+
+    def refs(self, i):
+        """holders of page i (0: free)"""
+        return self._ref.get(i, 0)
+
+    @property
+    def n_shared(self):
+        """pages with more than one holder"""
+        return sum(1 for v in self._ref.values() if v > 1)
 
     @property
     def n_free(self):
         return len(self._free)
+
+
+def prefix_key(image, seed, refer_boxes=None, ground_boxes=None, precision=None):
+    """what a prompt's image prefix depends on besides its ids: a digest of the image's bytes, the region-shuffle seed, the refer /
+    ground boxes and the model's precision.  None (no cache entry can be shared) without an explicit seed."""
+    if seed is None:
+        return None
+    h = hashlib.blake2b(digest_size=16)
+    for t in (image, refer_boxes, ground_boxes):
+        if t is None:
+            h.update(b"none;")
+            continue
+        t = t.detach().to("cpu").contiguous()
+        h.update(f"{t.dtype}{tuple(t.shape)};".encode())
+        h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes())
+    return (h.hexdigest(), int(seed), str(precision))
+
+
+@dataclass
+class PrefixEntry:
+    """one cached image prefix: the whole KV pages of a cold-admitted prompt and what a later suffix prefill needs again"""
+    key: tuple
+    ids: torch.Tensor            # un-expanded prompt ids (host)
+    ids_x: torch.Tensor          # expanded ids (host)
+    pred_boxes: torch.Tensor
+    pages: List[int]             # the prompt's whole pages (positions [0, 64 * len(pages)))
+    rows: Optional[torch.Tensor]  # f32 [L - e0, T]: the LLM input rows of positions [e0, L)
+    e0: int                      # first position of the page that holds the last injected (image / region) row
+
+
+@dataclass
+class PrefixMatch:
+    entry: PrefixEntry
+    u: int     # common prefix of the un-expanded ids
+    c: int     # its expanded length
+    p0: int    # the suffix prefill starts here (a page boundary inside the shared prefix)
+    L: int     # the request's expanded prompt length
+
+
+class PrefixCache:
+    """Host side of the prefix cache (no device work): entries in least-recently-used order, matching and eviction.  Entries hold
+    their pages in the PagePool (retain / release), so a page an evicted entry shared stays allocated while a live row maps it."""
+
+    def __init__(self, pool, placeholders, page=64):
+        self.pool, self.placeholders, self.page = pool, frozenset(int(x) for x in placeholders), page
+        self.entries = OrderedDict()   # id -> PrefixEntry, oldest use first
+        self._next = 0
+        self.evicted = 0
+
+    def __len__(self):
+        return len(self.entries)
+
+    def match(self, key, ids):
+        """the best entry of `key` for the un-expanded ids, or None (a miss).  The longest common prefix u of the ids must cover every
+        placeholder of the request; it expands to c positions and the suffix prefill starts at p0 = the last page boundary <= c (and
+        < L, the request's expanded length, so that at least its last position is computed); p0 = 0 is a miss."""
+        if key is None:
+            return None
+        ids_l = ids.tolist()
+        ph = [i for i, x in enumerate(ids_l) if x in self.placeholders]
+        best = None
+        for e in self.entries.values():
+            if e.key != key:
+                continue
+            eu = e.ids.tolist()
+            n = min(len(eu), len(ids_l))
+            u = 0
+            while u < n and eu[u] == ids_l[u]:
+                u += 1
+            if not ph or ph[-1] >= u:
+                continue
+            c = u + (len(e.ids_x) - len(eu))
+            L = c + len(ids_l) - u
+            p0 = self.page * (min(c, L - 1) // self.page)
+            if p0 == 0 or p0 < e.e0 or p0 > self.page * len(e.pages):
+                continue
+            if best is None or (p0, u) > (best.p0, best.u):
+                best = PrefixMatch(e, u, c, p0, L)
+        return best
+
+    def touch(self, e):
+        for k, v in self.entries.items():
+            if v is e:
+                self.entries.move_to_end(k)
+                return
+
+    def add(self, key, ids, ids_x, pred_boxes, pages, rows, e0):
+        """a new entry holding `pages` (retained here); an entry of the same key and ids is only touched"""
+        for k, v in self.entries.items():
+            if v.key == key and torch.equal(v.ids, ids):
+                self.entries.move_to_end(k)
+                return v
+        self.pool.retain(pages)
+        e = PrefixEntry(key, ids, ids_x, pred_boxes, list(pages), rows, int(e0))
+        self.entries[self._next] = e
+        self._next += 1
+        return e
+
+    def evict(self):
+        """drop the least recently used entry (its pages lose one holder).  False when there is none."""
+        if not self.entries:
+            return False
+        _, e = self.entries.popitem(last=False)
+        self.pool.release(e.pages)
+        self.evicted += 1
+        return True
+
+    def clear(self):
+        while self.evict():
+            pass
 
 
 @dataclass
@@ -126,6 +267,7 @@ class Request:
     done: bool = False
     error: Optional[str] = None
     pages: Optional[List[int]] = None       # paged mode: the pages reserved for this request (released when it finishes)
+    hit: Optional["PrefixMatch"] = None     # prefix cache: the cached prefix this request's suffix prefill continues
 
 
 class _RowView:
@@ -155,10 +297,14 @@ class _RowView:
 class ContinuousBatcher:
     @engine.model_entry(lambda self, *a, **kw: (a[0] if a else kw["model"]).precision)
     def __init__(self, model, max_rows=8, max_len=1024, use_graph=True, grow_to=None, overlap_admission=None, admit_min=2, admit_hold=8,
-                 kv_pages=None, admit_rows=None, max_prompt_len=None):
+                 kv_pages=None, admit_rows=None, max_prompt_len=None, prefix_cache=False):
         """kv_pages=N: a paged KV cache of N pages of 64 positions (engine.PagedKVCache) instead of max_rows slots of max_len positions;
         max_len is then the per-request cap.  admit_rows (default min(max_rows, 8)) bounds an admission wave, max_prompt_len (default
-        min(max_len, 1024)) the prompt part of a request: the staging cache the prefills land in holds admit_rows x max_prompt_len."""
+        min(max_len, 1024)) the prompt part of a request: the staging cache the prefills land in holds admit_rows x max_prompt_len.
+        prefix_cache=True (paged mode only): requests with an explicit seed that share an image prefix with an earlier one map its
+        whole KV pages and prefill only their suffix (see `_take_batch` / `_prefill_hits`)."""
+        if prefix_cache and kv_pages is None:
+            raise ValueError("prefix_cache needs a paged KV cache (kv_pages=N): cached prefixes are shared as whole pages")
         if max_rows < 1 or max_rows > 64:
             raise ValueError("max_rows must be in 1..64 (1..8: the fused 8-row weight streams; 9..64: the matrix-unit weight streams, "
                              "csrc/gemm_skinny.hip / gemm_skinny_fp8.hip -- single-type 16-bit or e4m3 models; others fall back to the general kernels)")
@@ -187,6 +333,15 @@ class ContinuousBatcher:
             self.arena = self.llm.new_cache(max_rows, max_len, dev)
             self.staging = self.llm.new_cache(max_rows, max_len, dev)  # batched prefills land here, then move to their slots
         self.slots = SlotTable(max_rows)
+        # prefix cache: entries + LRU on the host; the admission table the suffix prefills address (never the live table the captured
+        # step reads: a hit's row joins that one at placement)
+        self.prefix, self.prefix_hits, self.prefix_misses = None, 0, 0
+        if prefix_cache:
+            ph = [model.img_token_id, model.reg_token_id, model.refer_box_token_id, model.ground_box_token_id,
+                  model.refer_feat_token_id, model.pad_token_id]
+            self.prefix = PrefixCache(self.pages, [x for x in ph if x is not None])
+            self._inj = frozenset(int(x) for x in (model.img_token_id, model.reg_token_id, model.refer_feat_token_id) if x is not None)
+            self._adm_table = torch.zeros((self.admit_rows, max_len // 64), dtype=I32, device=dev)
         self.queue = deque()
         self.live = {}
         self._next_rid = 0
@@ -239,7 +394,14 @@ class ContinuousBatcher:
             return dict(pages_total=None, pages_free=None, high_water=None,
                         pool_bytes=sum(t.numel() * t.element_size() for t in self.arena.k + self.arena.vt), staging_bytes=st)
         return dict(pages_total=self.pages.n, pages_free=self.pages.n_free, high_water=self.pages.high_water,
-                    pool_bytes=self.arena.nbytes(), staging_bytes=st)
+                    pool_bytes=self.arena.nbytes(), staging_bytes=st,
+                    prefix_entries=len(self.prefix) if self.prefix is not None else 0, prefix_hits=self.prefix_hits,
+                    prefix_misses=self.prefix_misses, pages_shared=self.pages.n_shared)
+
+    def clear_prefix_cache(self):
+        """drop every prefix-cache entry; pages that live rows still map stay allocated until those rows finish"""
+        if self.prefix is not None:
+            self.prefix.clear()
 
     # ------------------------------------------------------------------ admission-time warm-up
     @engine.model_entry(lambda self, *a, **kw: self.model.precision)
@@ -371,9 +533,15 @@ class ContinuousBatcher:
         self._place(reqs, self._prefill(reqs))
 
     def _prefill(self, reqs):
-        """The device half of an admission, on the CURRENT stream: one batched forward into the staging cache + each row's first token.
-        Returns [(request, staging row, first token, 1/temperature)] for the requests that go on; touches neither the slot table nor
-        the arena nor the loop state (with overlap_admission it runs on the worker thread while the decode ticks use those)."""
+        """The device half of an admission, on the CURRENT stream: one batched forward into the staging cache + each row's first token
+        (prefix-cache hits: one suffix prefill on the paged cache, _prefill_hits).  Returns [(request, staging row or None, first token,
+        1/temperature)] for the requests that go on; touches neither the slot table nor the arena's table nor the loop state (with
+        overlap_admission it runs on the worker thread while the decode ticks use those)."""
+        cold = [r for r in reqs if r.hit is None]
+        hits = [r for r in reqs if r.hit is not None]
+        return (self._prefill_cold(cold) if cold else []) + (self._prefill_hits(hits) if hits else [])
+
+    def _prefill_cold(self, reqs):
         m, k = self.model, len(reqs)
         P = max(r.input_ids.numel() for r in reqs)
         ids = torch.full((k, P), int(m.pad_token_id), dtype=I64)
@@ -386,7 +554,7 @@ class ContinuousBatcher:
         try:
             out = m.forward(input_ids=ids, images=torch.stack([r.image for r in reqs]), refer_boxes=rb, ground_boxes=gb,
                             use_cache=True, return_dict=True, output_hidden_states=True, _cache=view,
-                            _seeds=[r.seed for r in reqs])
+                            _seeds=[r.seed for r in reqs], _keep_embeds=self.prefix is not None)
         except RuntimeError as e:
             if k == 1:
                 reqs[0].done, reqs[0].error = True, str(e)
@@ -395,7 +563,7 @@ class ContinuousBatcher:
             # batch-1 prefill lands in row 0 -- so the survivors are moved to their rows as they come
             placed = []
             for i in range(k - 1, -1, -1):   # (last to first: row 0 is where every batch-1 prefill lands, so its own request goes last)
-                one = self._prefill([reqs[i]])
+                one = self._prefill_cold([reqs[i]])
                 if one:
                     if i:
                         for l in range(len(self.staging.k)):
@@ -406,20 +574,93 @@ class ContinuousBatcher:
             return placed
         lengths = m._last_aux["lengths"]
         placed = []
-        dev = self.tok.device
         for i, r in enumerate(reqs):
             r.prompt_len = int(lengths[i])
             r.pred_boxes = out.hidden_states[1]["pred_boxes"][i]
             if r.prompt_len + r.max_new_tokens > self.max_len:
                 r.done, r.error = True, "prompt + max_new_tokens exceeds the KV slot (max_len)"
                 continue
-            it = 0.0 if r.temperature < 1e-4 else 1.0 / r.temperature
-            first = int(ops.sample_rows(out.logits[i, r.prompt_len - 1][None].contiguous(), out.logits.shape[-1],
-                                        torch.tensor([it], dtype=F32, device=dev),
-                                        torch.tensor([int(r.seed or 0)], dtype=I64, device=dev),
-                                        pos=torch.tensor([r.prompt_len], dtype=I32, device=dev))[0])
-            placed.append((r, i, first, it))
+            if self.prefix is not None:
+                self._keep_prefix(r, m._last_aux["input_ids"][i, : r.prompt_len], m._last_aux["inputs_embeds"][i])
+            placed.append((r, i) + self._first_token(r, out.logits[i, r.prompt_len - 1]))
         return placed
+
+    def _first_token(self, r, logits_row):
+        """(first token, 1/temperature) of a request from the logits of its last prompt position"""
+        dev = self.tok.device
+        it = 0.0 if r.temperature < 1e-4 else 1.0 / r.temperature
+        first = int(ops.sample_rows(logits_row[None].contiguous(), logits_row.shape[-1],
+                                    torch.tensor([it], dtype=F32, device=dev),
+                                    torch.tensor([int(r.seed or 0)], dtype=I64, device=dev),
+                                    pos=torch.tensor([r.prompt_len], dtype=I32, device=dev))[0])
+        return first, it
+
+    # ------------------------------------------------------------------ prefix cache
+    def _keep_prefix(self, r, ids_x, emb):
+        """a cold request that may become a prefix-cache entry at placement: keep its expanded ids and the LLM input rows from the page
+        of its last injected (image / region) row to the end of the prompt -- the only prefix rows a later suffix prefill recomputes"""
+        r._entry = None
+        key = getattr(r, "_key", None)
+        xs = ids_x.tolist()
+        inj = [j for j, x in enumerate(xs) if x in self._inj]
+        if key is None or not inj or r.prompt_len < 64 or self.model.pad_token_id in r.input_ids.tolist():
+            return
+        e0 = 64 * (inj[-1] // 64)
+        r._entry = (key, ids_x.clone(), emb[e0: r.prompt_len].clone(), e0)
+
+    def _match(self, r):
+        """paged mode with the cache on: the request's PrefixMatch, or None (a cold admission).  A hit's suffix, padded to the wave's
+        common length, must stay inside max_len (the RoPE tables): a hit that could not is run cold."""
+        m = self.model
+        r._key = key = prefix_key(r.image, r.seed, r.refer_boxes, r.ground_boxes,
+                                  (m.precision, getattr(m, "vit_precision", None), bool(self.llm.w["fp8"])))
+        if key is None:
+            return None
+        hit = self.prefix.match(key, r.input_ids)
+        if hit is None or hit.L + r.max_new_tokens > self.max_len or hit.p0 + max(9, hit.L - hit.p0) > self.max_len:
+            return None
+        return hit
+
+    def _prefill_hits(self, reqs):
+        """One suffix prefill for the prefix-cache hits of a wave, on the CURRENT stream: row b prefills positions [p0_b, L_b) on the
+        paged cache through the admission table (its entry's shared pages below p0_b, then its own), from the entry's stored input rows
+        of [p0_b, c_b) and the embeddings of its own ids behind the shared prefix.  Rows are padded to a common length (at least 2 and
+        more than 8 rows in all: the prefill GEMM forms); what a padding position writes lands in a page of its own row or in the sink
+        page.  Returns the placed tuples, first tokens sampled as _prefill_cold samples them."""
+        groups = []   # (a padded position must stay below max_len, the RoPE tables' bound: rare waves split, _match admits every row alone)
+        for r in reqs:
+            for g in groups:
+                if all(x.hit.p0 + self._wave_len(g + [r]) <= self.max_len for x in g + [r]):
+                    g.append(r)
+                    break
+            else:
+                groups.append([r])
+        return [p for g in groups for p in self._suffix_prefill(g)]
+
+    @staticmethod
+    def _wave_len(reqs):
+        """the common suffix length of a wave: its longest suffix, at least 2 and more than 8 rows in all (the prefill GEMM forms)"""
+        return max(max(r.hit.L - r.hit.p0 for r in reqs), 2, -(-9 // len(reqs)))
+
+    def _suffix_prefill(self, reqs):
+        llm, dev, T = self.llm, self.tok.device, self.llm.T
+        k = len(reqs)
+        Lq = self._wave_len(reqs)
+        h = torch.zeros((k * Lq, T), dtype=F32, device=dev)
+        tab = torch.zeros((k, self._adm_table.shape[1]), dtype=I32)
+        for b, r in enumerate(reqs):
+            m, e = r.hit, r.hit.entry
+            r.prompt_len = m.L
+            r.pred_boxes = e.pred_boxes.clone()
+            h[b * Lq: b * Lq + m.c - m.p0].copy_(e.rows[m.p0 - e.e0: m.c - e.e0])
+            if m.L > m.c:
+                llm.embed(r.input_ids[m.u:].to(dev), out=h[b * Lq + m.c - m.p0: b * Lq + m.L - m.p0])
+            tab[b, : len(r.pages)] = torch.tensor(r.pages, dtype=I32)
+        self._adm_table[:k].copy_(tab)
+        pos = torch.tensor([r.hit.p0 for r in reqs], dtype=I32).to(dev)
+        kv_len = torch.tensor([r.hit.L for r in reqs], dtype=I32).to(dev)
+        logits = llm.prefill_paged(h, k, Lq, self.arena, self._adm_table, pos, kv_len)
+        return [(r, None) + self._first_token(r, logits[b, r.hit.L - 1 - r.hit.p0]) for b, r in enumerate(reqs)]
 
     def _place(self, reqs, placed):
         """The host half of an admission, on the decode stream between two ticks: emit the first tokens, hand out slots, move the rows'
@@ -459,7 +700,7 @@ class ContinuousBatcher:
             if r.slot is None:
                 if r.pages:
                     self.pages.release(r.pages)
-                r.pages = None
+                r.pages, r._entry = None, None
                 continue
             keep = -(-(r.prompt_len + r.max_new_tokens) // 64)
             if keep < len(r.pages):
@@ -474,11 +715,22 @@ class ContinuousBatcher:
             tab[j, : len(r.pages)] = torch.tensor(r.pages, dtype=I32)
         slots = torch.tensor([r.slot for r in live], dtype=I64, device=dev)
         self.arena.table.index_copy_(0, slots, tab.to(dev))
-        meta = torch.tensor([rows, [r.slot for r in live], [r.prompt_len for r in live]], dtype=I32).to(dev)
-        n = max(r.prompt_len for r in live)
+        # prefix-cache hits prefilled straight into their pages: only the cold rows come from the staging cache
+        cold = [(r, i) for r, i, _, _ in placed if r.slot is not None and i is not None]
+        if not cold:
+            return
+        meta = torch.tensor([[i for _, i in cold], [r.slot for r, _ in cold], [r.prompt_len for r, _ in cold]], dtype=I32).to(dev)
+        n = max(r.prompt_len for r, _ in cold)
         for l in range(len(self.arena.k)):
             ops.kv_scatter_pages(self.staging.k[l], self.staging.vt[l], self.arena.k[l], self.arena.vt[l], self.arena.table, meta,
                                  min(n, self.max_prompt_len))
+        if self.prefix is not None:   # a cold prompt's whole pages become an entry
+            for r, _ in cold:
+                kept = getattr(r, "_entry", None)
+                r._entry = None
+                if kept is not None:
+                    key, ids_x, rows, e0 = kept
+                    self.prefix.add(key, r.input_ids, ids_x, r.pred_boxes.clone(), r.pages[: r.prompt_len // 64], rows, e0)
 
     def _take_batch(self):
         """the requests of the next admission wave, off the head of the queue.  Slot mode: as many as there are free slots.  Paged mode:
@@ -503,13 +755,40 @@ class ContinuousBatcher:
                 r.done, r.error = True, err
                 refused.append(r)
                 continue
-            ids = self.pages.reserve(need)
+            if self.prefix is not None:
+                ids = self._reserve_prefixed(r, need)
+            else:
+                ids = self.pages.reserve(need)
             if ids is None:
                 break
             self.queue.popleft()
             r.pages = ids
             batch.append(r)
         return batch, refused
+
+    def _reserve_prefixed(self, r, need):
+        """prefix cache on: the request's pages -- a hit maps its entry's pages below p0 (one more holder each) and reserves the rest of
+        its exact context; a miss reserves `need` as without the cache.  Least recently used entries are evicted while a reservation
+        cannot be met.  None (nothing held) when it cannot be met without them either."""
+        hit = self._match(r)
+        shared = hit.entry.pages[: hit.p0 // 64] if hit is not None else []
+        if hit is not None:
+            self.pages.retain(shared)   # (before any eviction: the entry may be the one evicted)
+            self.prefix.touch(hit.entry)
+            need = -(-(hit.L + r.max_new_tokens) // 64) - len(shared)
+        ids = self.pages.reserve(need)
+        while ids is None and self.prefix.evict():
+            ids = self.pages.reserve(need)
+        if ids is None:
+            if shared:
+                self.pages.release(shared)
+            return None
+        r.hit = hit
+        if hit is not None:
+            self.prefix_hits += 1
+        else:
+            self.prefix_misses += 1
+        return shared + ids
 
     # ------------------------------------------------------------------ overlapped admission (worker thread + side stream)
     def _launch_admission(self, reqs):
@@ -518,6 +797,10 @@ class ContinuousBatcher:
         if self._placed is not None:
             self._side.wait_event(self._placed)   # the previous batch has left the staging cache
         else:
+            self._side.wait_stream(torch.cuda.current_stream())
+        if any(r.hit is not None for r in reqs):
+            # a suffix prefill writes pages straight away: behind the decode stream's last table update (pages freed by rows that
+            # finished since) and every placement that filled the pages it maps
             self._side.wait_stream(torch.cuda.current_stream())
 
         job["thread"] = threading.Thread(target=self._admission_work, args=(job,), name="groma-admission", daemon=True)

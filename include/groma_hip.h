@@ -190,6 +190,21 @@ int gr_qkv_split_paged(const void* qkv, void* q, void* k_pool, void* vt_pool, co
 int gr_kv_scatter_pages(const void* k_src, const void* vt_src, void* k_pool, void* vt_pool, const int* block_table, int table_ld,
                         const int* src_rows, const int* dst_rows, const int* lens, int n, int n_src, int n_dst, int H, int S,
                         int head_dim, int max_len, hipStream_t stream);
+/* ABI 9, additive: the K / V^T write of a multi-position prefill into a paged cache (the suffix prefill of a prefix-cache hit).
+ * qkv: the fused projection rows [B*L, 3*H*hd]; row b's positions pos0_b + i (i < L; pos0_b = pos_dev ? pos_dev[b * pos_stride]
+ * : pos0) get HF rotate_half-RoPE'd K rows and V^T columns in the pages of block_table row b (positions past the table: the sink
+ * page 0).  q is not written.  The same values as gr_qkv_split writes into a slot cache.  table_ld <= 128; GR_EINVAL in the
+ * operand-pair build. */
+int gr_kv_append_paged(const void* qkv, void* k_pool, void* vt_pool, const float* cosT, const float* sinT, int B, int H, int L,
+                       int head_dim, int pos0, const int* block_table, int table_ld, const int* pos_dev, int pos_stride,
+                       hipStream_t stream);
+/* ABI 9, additive: causal attention of Lq queries per row over a paged cache.  Row b's queries sit at q_pos0_b + i (q_pos0_b as
+ * above) and see keys 0 .. q_pos0_b + i that are < kv_len[b] (if given), key s in page block_table[b * table_ld + s / 64]; q, q_ld,
+ * rope_cos / rope_sin and out as for gr_attention_bf16.  head_dim 128 or 64, table_ld * 64 <= 8192.  The same bits as
+ * gr_attention_bf16 over a slot cache that holds the same keys.  GR_EINVAL in the operand-pair build. */
+int gr_attention_paged(const void* q, const void* k_pool, const void* vt_pool, void* out, const int* kv_len, int B, int H, int Lq,
+                       const int* block_table, int table_ld, int head_dim, int q_pos0, float scale, const int* pos_dev,
+                       int pos_stride, long q_ld, const float* rope_cos, const float* rope_sin, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------ decode step -- */
 /* One new token per row (groma/model/groma.py:376-379 + HF LlamaDecoderLayer at L = 1): gr_gemv_fused (above) streams each
