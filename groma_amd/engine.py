@@ -8,6 +8,7 @@ LlamaEngine      HF LlamaModel + heads, groma.py:389-402                       a
 Residual streams are fp32 in HBM; GEMM operands bf16 (fp32 accumulate); the proposer is fp32 end to end.
 """
 import collections
+import copy
 import math
 
 import torch
@@ -18,7 +19,6 @@ F32, I32, I64 = torch.float32, torch.int32, torch.int64
 H16 = ops.H16  # dtype of the active 16-bit operand type (bf16 / fp16: ops.precision)
 
 
-Q_IN_PLACE = True  # prefill attention reads q (and applies RoPE) straight from the fused QKV projection
 FUSED_DECODE = True  # a decode step of <= 8 rows runs on the fused weight streams (False: the general kernels -- tests compare the two)
 WIDE_DECODE = True   # a decode step of 9..64 rows runs on the matrix-unit weight stream (csrc/gemm_skinny.hip); False: the general kernels
 YIELD_PYRAMID = True  # the region pyramid's convolutions (side stream) run one workgroup per tile, so the proposer chain on the main stream is not
@@ -269,6 +269,41 @@ class GraphPool:
         self._graphs.clear(), self._seen.clear(), self._bytes.clear()
 
 
+class _Operands:
+    """The activation operand of a GEMM on the general kernels -- the one rule every such layer loop shares.  e4m3 models: a norm
+    output quantised straight from the fp32 rows (gr_norm_fp8), a stored 16-bit activation through the row quantiser, into the
+    never-moved q8 buffers {K: (rows, scales)}, with dynamic per-row activation scales.  16-bit models: the norm into the x buffer, a
+    stored activation as it is, with the caller-owned split-K workspace.  Weights are (w, w_scale) pairs; tag: the TRACE name of the
+    operand (layer 0 of a stage)."""
+
+    def __init__(self, fp8, eps, layernorm, q8, x, split_ws=None, tile=0):
+        self.fp8, self.eps, self.layernorm, self.q8, self.x, self.split_ws, self.tile = fp8, eps, layernorm, q8, x, split_ws, tile
+
+    def _gemm8(self, a8, wt, tag, kw):
+        _trace_q8(tag, *a8)
+        return ops.gemm(a8[0], wt[0], a_scale=a8[1], w_scale=wt[1], tile=self.tile, **kw)
+
+    def norm_gemm(self, x_f32, gain, wt, beta=None, tag=None, xb=None, **kw):
+        """RMSNorm (LayerNorm with beta) of fp32 rows -> GEMM; xb: the 16-bit norm output instead of x"""
+        if self.fp8:
+            a8 = ops.norm_fp8(x_f32, gain, beta, self.eps, not self.layernorm, out=self.q8[x_f32.shape[-1]])
+            return self._gemm8(a8, wt, tag, kw)
+        xb = self.x if xb is None else xb
+        if self.layernorm:
+            x = ops.layernorm(x_f32, gain, beta, self.eps, out_bf16=True, out=xb)
+        else:
+            x = ops.rmsnorm(x_f32, gain, self.eps, out=xb)
+        if tag:
+            _trace(tag, x)
+        return ops.gemm(x, wt[0], split_ws=self.split_ws, tile=self.tile, **kw)
+
+    def gemm(self, a16, wt, tag=None, **kw):
+        """stored 16-bit activation -> GEMM"""
+        if self.fp8:
+            return self._gemm8(ops.quant_rows_fp8(a16, out=self.q8[a16.shape[-1]]), wt, tag, kw)
+        return ops.gemm(a16, wt[0], split_ws=self.split_ws, tile=self.tile, **kw)
+
+
 # ------------------------------------------------------------------------------------------------ DINOv2
 class VitEngine:
     def __init__(self, w, cfg, ws):
@@ -305,7 +340,6 @@ class VitEngine:
         kept = [ws.get(f"vit_h{i}", (bs, T, D), F32) for i in range(self.keep)]
         scratch = [ws.get(f"vit_s{i}", (bs, T, D), F32) for i in range(2)]
         mid = ws.get("vit_mid", (bs, T, D), F32)
-        q = None if Q_IN_PLACE else ws.get("vit_q", h16(bs, H, T, hd), H16())
         k = ws.get("vit_k", h16(bs, H, Tp, hd), H16(), zero=True)
         vt = ws.get("vit_vt", h16(bs, H, hd, Tp), H16(), zero=True)
         x_b = ws.get("vit_x", h16(M, D), H16())
@@ -324,23 +358,7 @@ class VitEngine:
             j = layer_out_index - (nl + 1 - self.keep)
             return kept[j] if j >= 0 else scratch[layer_out_index & 1]
 
-        def lin(x_f32, ln_g, ln_b, wt, tag=None, **kw):
-            """LayerNorm -> GEMM (bf16 operands, or e4m3 operands with dynamic per-row activation scales)"""
-            if fp8:
-                x8, sx = ops.norm_fp8(x_f32, ln_g, ln_b, self.eps, False, out=q8[x_f32.shape[-1]])
-                _trace_q8(tag, x8, sx)
-                return ops.gemm(x8, wt[0], a_scale=sx, w_scale=wt[1], **kw)
-            x = ops.layernorm(x_f32, ln_g, ln_b, self.eps, out_bf16=True, out=x_b)
-            if tag:
-                _trace(tag, x)
-            return ops.gemm(x, wt[0], split_ws=skw, **kw)
-
-        def lin_bf16(x_bf16, wt, tag=None, **kw):
-            if fp8:
-                x8, sx = ops.quant_rows_fp8(x_bf16, out=q8[x_bf16.shape[-1]])
-                _trace_q8(tag, x8, sx)
-                return ops.gemm(x8, wt[0], a_scale=sx, w_scale=wt[1], **kw)
-            return ops.gemm(x_bf16, wt[0], split_ws=skw, **kw)
+        op = _Operands(fp8, self.eps, True, q8, x_b, skw)
 
         def launch():
             ops.patchify(img, self.P, w["Kpad"], out=a)
@@ -352,25 +370,23 @@ class VitEngine:
                 t0 = TRACE is not None and i == 0
                 if t0:
                     _trace("vit0.h_in", h)
-                qkv = lin(h, L["ln1_g"], L["ln1_b"], L["wqkv"], tag="vit0.ln1" if t0 else None, bias=L["bqkv"], out=qkv_b)
-                ops.qkv_split(qkv, q, k, vt, B=bs, H=H, L=T, hd=hd)
-                if Q_IN_PLACE:  # attention reads q straight from the fused projection
-                    ctx = ops.attention(qkv, k, vt, Skv=T, causal=False, out=ctx_b, fused=dict(B=bs, H=H, Lq=T, hd=hd))
-                else:
-                    ctx = ops.attention(q, k, vt, Skv=T, causal=False, out=ctx_b)
-                lin_bf16(ctx, L["wo"], tag="vit0.ctx" if t0 else None, bias=L["bo"], scale=L["ls1"], resid=h, out=mid,
-                         out_f32=True)
-                y = lin(mid, L["ln2_g"], L["ln2_b"], L["w1"], tag="vit0.ln2" if t0 else None, bias=L["b1"], act=1, out=y_b)
+                qkv = op.norm_gemm(h, L["ln1_g"], L["wqkv"], beta=L["ln1_b"], tag="vit0.ln1" if t0 else None, bias=L["bqkv"],
+                                   out=qkv_b)
+                ops.qkv_split(qkv, None, k, vt, B=bs, H=H, L=T, hd=hd)
+                # attention reads q straight from the fused projection
+                ctx = ops.attention(qkv, k, vt, Skv=T, causal=False, out=ctx_b, fused=dict(B=bs, H=H, Lq=T, hd=hd))
+                op.gemm(ctx, L["wo"], tag="vit0.ctx" if t0 else None, bias=L["bo"], scale=L["ls1"], resid=h, out=mid, out_f32=True)
+                y = op.norm_gemm(mid, L["ln2_g"], L["w1"], beta=L["ln2_b"], tag="vit0.ln2" if t0 else None, bias=L["b1"], act=1,
+                                 out=y_b)
                 hn = out_buf(i + 1)
-                lin_bf16(y, L["w2"], tag="vit0.fc1" if t0 else None, bias=L["b2"], scale=L["ls2"], resid=mid, out=hn,
-                         out_f32=True)
+                op.gemm(y, L["w2"], tag="vit0.fc1" if t0 else None, bias=L["b2"], scale=L["ls2"], resid=mid, out=hn, out_f32=True)
                 if t0:
                     _trace("vit0.qkv", qkv), _trace("vit0.ctx", ctx), _trace("vit0.mid", mid), _trace("vit0.fc1", y)
                     _trace("vit0.out", hn)
                 h = hn
 
         if graph:
-            bufs = [img, a, mid, k, vt, x_b, qkv_b, ctx_b, y_b] + kept + scratch + ([] if q is None else [q]) + ([] if skw is None else [skw]) \
+            bufs = [img, a, mid, k, vt, x_b, qkv_b, ctx_b, y_b] + kept + scratch + ([] if skw is None else [skw]) \
                 + [t for pair in q8.values() for t in pair]
             self.graphs.run(("vit", bs, ops._PLAN[0], fp8) + tuple(t.data_ptr() for t in bufs), launch)
         else:
@@ -598,13 +614,22 @@ class RegionEngine:
 class KVCache:
     """Device KV cache: K [bs,H,Smax,hd], V transposed [bs,H,hd,Smax] per layer.  Indexing gives the reference's legacy
     tuple view: cache[l][0].shape == [bs, H, S, hd] (groma/model/groma.py:377-378, groma/serve/model_worker.py:298)."""
+    paged, table = False, None   # (the slot layout: row b's positions are row b of every layer's K / V^T)
 
     def __init__(self, n_layers, bs, H, hd, smax, device):
         self.k = [torch.zeros(h16(bs, H, smax, hd), dtype=H16(), device=device) for _ in range(n_layers)]
         self.vt = [torch.zeros(h16(bs, H, hd, smax), dtype=H16(), device=device) for _ in range(n_layers)]
         self.seq_len, self.smax, self.bs = 0, smax, bs
         self.sp = ops.SP()  # 2: (hi, lo) operand pairs, innermost extents doubled (precision "ref")
-        self._addr = None
+        self._addr, self._fixed = None, False
+
+    def rows(self, n):
+        """the first n rows of this cache as a KVCache over the same memory, empty and unable to grow: GromaModel.forward prefills
+        straight into it (the continuous batcher's staging cache)"""
+        v = copy.copy(self)
+        v.k, v.vt = [t[:n] for t in self.k], [t[:n] for t in self.vt]
+        v.seq_len, v.bs, v._addr, v._fixed = 0, n, None, True
+        return v
 
     def __len__(self):
         return len(self.k)
@@ -621,6 +646,8 @@ class KVCache:
     def grow(self, smax):
         if smax <= self.smax:
             return
+        if self._fixed:
+            raise RuntimeError("a KV slot cannot grow: the request exceeds max_len")
         for l in range(len(self.k)):
             k = torch.zeros((self.bs,) + tuple(self.k[l].shape[1:2]) + (smax, self.k[l].shape[3]), dtype=self.k[l].dtype,
                             device=self.k[l].device)
@@ -638,7 +665,7 @@ class PagedKVCache:
     table[b, s // 64] of every layer's pools.  Page 0 is the sink page: never handed to a request, every unowned table entry points
     at it, so what masked rows write lands there.  Neither the pools nor the table ever move (a captured decode step stays valid);
     the table's contents change in place.  Only the decode step (L = 1, weight-streaming kernels) reads or writes it."""
-    paged = True
+    paged, sp = True, 1
     PAGE = 64
 
     def __init__(self, n_layers, rows, H, hd, smax, n_pages, device):
@@ -647,7 +674,7 @@ class PagedKVCache:
         self.k = [torch.zeros((n_pages + 1, H, 64, hd), dtype=H16(), device=device) for _ in range(n_layers)]
         self.vt = [torch.zeros((n_pages + 1, H, hd, 64), dtype=H16(), device=device) for _ in range(n_layers)]
         self.table = torch.zeros((rows, smax // 64), dtype=I32, device=device)
-        self.seq_len, self.smax, self.bs, self.n_pages, self.sp = 0, smax, rows, n_pages, 1
+        self.seq_len, self.smax, self.bs, self.n_pages = 0, smax, rows, n_pages
         self._addr = None
 
     def __len__(self):
@@ -730,7 +757,7 @@ class LlamaEngine:
         dyn = pos_dev is not None
         past = 0 if dyn else cache.seq_len
         path = self.decode_path(M, cache.smax, L, states)
-        if getattr(cache, "paged", False) and (path is None or not dyn or bs > cache.bs):
+        if cache.paged and (path is None or not dyn or bs > cache.bs):
             # the general kernels (and every L > 1 path) address a slot arena: never hand them the pools of a paged cache
             raise ValueError("a paged KV cache is read and written only by the decode step of the weight-streaming kernels "
                              "(L = 1, <= 64 rows, device-resident positions, a single-type 16-bit or e4m3 stack)")
@@ -752,7 +779,6 @@ class LlamaEngine:
         fp8 = w["fp8"]
         st = self._st
         with st("attn"):
-            q = None if Q_IN_PLACE else buf("llm_q", h16(bs, H, L, hd), H16())
             x_b, qkv_b = buf("llm_x", h16(M, T), H16()), buf("llm_qkv", h16(M, 3 * T), H16())
             ctx_b = buf("llm_ctx", h16(M, T), H16())
         with st("mlp"):
@@ -770,58 +796,20 @@ class LlamaEngine:
             kvl = ws.get("llm_kvlen", (bs,), I32)
             kvl.copy_(kv_len)
             kv_len = kvl
+        op = _Operands(fp8, self.eps, False, q8, x_b, skw)
 
-        def lin(x_f32, gain, wt, tag=None, xb=None, **kw):
-            """RMSNorm -> GEMM (bf16 operands, or e4m3 operands with dynamic per-row activation scales)"""
-            if fp8:
-                x8, sx = ops.norm_fp8(x_f32, gain, None, self.eps, True, out=q8[x_f32.shape[-1]])
-                _trace_q8(tag, x8, sx)
-                return ops.gemm(x8, wt[0], a_scale=sx, w_scale=wt[1], **kw)
-            x = ops.rmsnorm(x_f32, gain, self.eps, out=x_b if xb is None else xb)
-            if tag:
-                _trace(tag, x)
-            return ops.gemm(x, wt[0], split_ws=skw, **kw)
-
-        def lin_bf16(x_bf16, wt, tag=None, **kw):
-            if fp8:
-                x8, sx = ops.quant_rows_fp8(x_bf16, out=q8[x_bf16.shape[-1]])
-                _trace_q8(tag, x8, sx)
-                return ops.gemm(x8, wt[0], a_scale=sx, w_scale=wt[1], **kw)
-            return ops.gemm(x_bf16, wt[0], split_ws=skw, **kw)
+        def attend(i, qkv):   # q is read (and rotated) in place from the fused projection: no packed q copy, no round trip
+            ops.qkv_split(qkv, None, cache.k[i], cache.vt[i], B=bs, H=H, L=L, hd=hd, pos0=past, cos=w["cos"], sin=w["sin"],
+                          pos_dev=pos_dev, pos_stride=pos_stride)
+            return ops.attention(qkv, cache.k[i], cache.vt[i], Skv=cache.smax if dyn else past + L, causal=True, q_pos0=past,
+                                 kv_len=kv_len, out=ctx_b, pos_dev=pos_dev, pos_stride=pos_stride,
+                                 fused=dict(B=bs, H=H, Lq=L, hd=hd, cos=w["cos"], sin=w["sin"]))
 
         def launch():
-            for i, Lw in enumerate(w["layers"]):
-                t0 = TRACE is not None and i == 0
-                if t0:
-                    _trace("llm0.h_in", h)
-                if states is not None:
-                    states.append(h.view(bs, L, T).clone())
-                with st("attn"):
-                    qkv = lin(h, Lw["n1"], Lw["wqkv"], tag="llm0.n1" if t0 else None, out=qkv_b)
-                    ops.qkv_split(qkv, q, cache.k[i], cache.vt[i], B=bs, H=H, L=L, hd=hd, pos0=past,
-                                  cos=w["cos"], sin=w["sin"], pos_dev=pos_dev, pos_stride=pos_stride)
-                    att_kw = dict(Skv=cache.smax if dyn else past + L, causal=True, q_pos0=past, kv_len=kv_len,
-                                  out=ctx_b, pos_dev=pos_dev, pos_stride=pos_stride)
-                    if Q_IN_PLACE:  # q is read (and rotated) in place: no packed q copy, no round trip
-                        ctx = ops.attention(qkv, cache.k[i], cache.vt[i],
-                                            fused=dict(B=bs, H=H, Lq=L, hd=hd, cos=w["cos"], sin=w["sin"]), **att_kw)
-                    else:
-                        ctx = ops.attention(q, cache.k[i], cache.vt[i], **att_kw)
-                    if t0:
-                        _trace("llm0.qkv", qkv), _trace("llm0.ctx", ctx)
-                    lin_bf16(ctx, Lw["wo"], tag="llm0.ctx" if t0 else None, resid=h, out=h, out_f32=True)
-                if t0:
-                    _trace("llm0.h_attn", h)
-                with st("mlp"):
-                    y = lin(h, Lw["n2"], Lw["wgu"], tag="llm0.n2" if t0 else None, xb=x2_b, act=3, out=y_b)
-                    if t0:
-                        _trace("llm0.act", y)
-                    lin_bf16(y, Lw["wd"], tag="llm0.act" if t0 else None, resid=h, out=h, out_f32=True)
-                if t0:
-                    _trace("llm0.h_out", h)
+            self._layers(h, op, attend, qkv_b, y_b, x2_b, trace=True, states=states, L=L)
 
         if graph:
-            bufs = [h, x_b, x2_b, qkv_b, ctx_b, y_b] + ([] if q is None else [q]) + ([] if kv_len is None else [kv_len]) + ([] if skw is None else [skw]) \
+            bufs = [h, x_b, x2_b, qkv_b, ctx_b, y_b] + ([] if kv_len is None else [kv_len]) + ([] if skw is None else [skw]) \
                 + [t for pair in q8.values() for t in pair]
             self.graphs.run(("llm", bs, L, past, kv_len is None, ops._PLAN[0], fp8, ops.SP()) + tuple(t.data_ptr() for t in bufs)
                             + cache_addresses(cache), launch)
@@ -831,6 +819,35 @@ class LlamaEngine:
             cache.seq_len = past + L
         with st("head"):
             return self._head(h, bs, L, xh_b, all_logits)
+
+    def _layers(self, h, op, attend, qkv_b, y_b, x2_b=None, trace=False, states=None, L=1):
+        """The LLaMA layers on the general kernels (forward's prefill and decode, prefill_paged, the wide decode step) over the fp32
+        residual rows h, updated in place: RMSNorm -> QKV, attend(i, qkv) -> ctx (layer i's KV write and attention), o-proj (+ h),
+        RMSNorm -> gate / up (SwiGLU), down (+ h).  op (_Operands) forms every GEMM operand, so each caller runs the same GEMMs, norms
+        and summation orders; x2_b: the mlp stage's norm output when it differs from op.x.  trace: the layer-0 TRACE tags are
+        recorded; states: receives the residual stream [bs, L, T] in front of every layer."""
+        st, T = self._st, self.T
+        for i, Lw in enumerate(self.w["layers"]):
+            t0 = trace and TRACE is not None and i == 0
+            if t0:
+                _trace("llm0.h_in", h)
+            if states is not None:
+                states.append(h.view(-1, L, T).clone())
+            with st("attn"):
+                qkv = op.norm_gemm(h, Lw["n1"], Lw["wqkv"], tag="llm0.n1" if t0 else None, out=qkv_b)
+                ctx = attend(i, qkv)
+                if t0:
+                    _trace("llm0.qkv", qkv), _trace("llm0.ctx", ctx)
+                op.gemm(ctx, Lw["wo"], tag="llm0.ctx" if t0 else None, resid=h, out=h, out_f32=True)
+            if t0:
+                _trace("llm0.h_attn", h)
+            with st("mlp"):
+                y = op.norm_gemm(h, Lw["n2"], Lw["wgu"], tag="llm0.n2" if t0 else None, xb=x2_b, act=3, out=y_b)
+                if t0:
+                    _trace("llm0.act", y)
+                op.gemm(y, Lw["wd"], tag="llm0.act" if t0 else None, resid=h, out=h, out_f32=True)
+            if t0:
+                _trace("llm0.h_out", h)
 
     def _head(self, h, bs, L, x_b, all_logits):
         """a21: final RMSNorm -> lm_head (+) extra_lm_head (under the head stage's operand type)"""
@@ -869,11 +886,11 @@ class LlamaEngine:
         `table` (int32 [>= bs, table_ld]: an admission table of the caller's, not the live table the captured decode step reads), and
         each query attends to keys 0 .. its position through it -- pages mapped from other rows included.  kv_len (i32 [bs]): row b's
         keys end there (right padding of ragged suffixes; what a padding position writes lands in a page the row owns or in the sink
-        page).  Returns the logits of every suffix row, f32 [bs, Lq, V].  Same GEMMs, norms and summation orders as forward()'s
-        prefill, so a row's logits are bitwise those of the same positions of a full prefill."""
+        page).  Returns the logits of every suffix row, f32 [bs, Lq, V].  The layers are forward()'s prefill layers (_layers, the same
+        operands), so a row's logits are bitwise those of the same positions of a full prefill."""
         w, ws, T, H, hd = self.w, self.ws, self.T, self.H, self.hd
         M = bs * Lq
-        if not getattr(cache, "paged", False) or self.prec is not None or ops.SP() != 1:
+        if not cache.paged or self.prec is not None or ops.SP() != 1:
             raise ValueError("prefill_paged needs a PagedKVCache and a single-type 16-bit or e4m3 stack")
         if Lq < 2 or M <= 8 or table.shape[0] < bs or pos_dev is None:
             # (M <= 8 would put the 16-bit GEMMs on the decode-step weight stream: another summation order than a full prefill's)
@@ -885,33 +902,37 @@ class LlamaEngine:
         skw = ws.get("sfx_splitk", (n_sk,), F32) if n_sk else None
         q8 = {K_: (ws.get(f"sfx_q8_{K_}", (M, K_), ops.FP8), ws.get(f"sfx_s8_{K_}", (M,), F32)) for K_ in ((T, self.I) if fp8 else ())}
 
-        def lin(x_f32, gain, wt, **kw):
-            if fp8:
-                x8, sx = ops.norm_fp8(x_f32, gain, None, self.eps, True, out=q8[x_f32.shape[-1]])
-                return ops.gemm(x8, wt[0], a_scale=sx, w_scale=wt[1], **kw)
-            return ops.gemm(ops.rmsnorm(x_f32, gain, self.eps, out=x_b), wt[0], split_ws=skw, **kw)
-
-        def lin_bf16(x_bf16, wt, **kw):
-            if fp8:
-                x8, sx = ops.quant_rows_fp8(x_bf16, out=q8[x_bf16.shape[-1]])
-                return ops.gemm(x8, wt[0], a_scale=sx, w_scale=wt[1], **kw)
-            return ops.gemm(x_bf16, wt[0], split_ws=skw, **kw)
-
-        for i, Lw in enumerate(w["layers"]):
-            qkv = lin(h, Lw["n1"], Lw["wqkv"], out=qkv_b)
+        def attend(i, qkv):
             ops.kv_append_paged(qkv, cache.k[i], cache.vt[i], table, B=bs, H=H, L=Lq, hd=hd, cos=w["cos"], sin=w["sin"],
                                 pos_dev=pos_dev, pos_stride=1)
-            ctx = ops.attention_paged(qkv, cache.k[i], cache.vt[i], table, B=bs, H=H, Lq=Lq, hd=hd, kv_len=kv_len, out=ctx_b,
-                                      pos_dev=pos_dev, pos_stride=1, cos=w["cos"], sin=w["sin"], fused=True)
-            lin_bf16(ctx, Lw["wo"], resid=h, out=h, out_f32=True)
-            y = lin(h, Lw["n2"], Lw["wgu"], act=3, out=y_b)
-            lin_bf16(y, Lw["wd"], resid=h, out=h, out_f32=True)
+            return ops.attention_paged(qkv, cache.k[i], cache.vt[i], table, B=bs, H=H, Lq=Lq, hd=hd, kv_len=kv_len, out=ctx_b,
+                                       pos_dev=pos_dev, pos_stride=1, cos=w["cos"], sin=w["sin"], fused=True)
+
+        self._layers(h, _Operands(fp8, self.eps, False, q8, x_b, skw), attend, qkv_b, y_b)
         return self._head(h, bs, Lq, x_b, True)[0]
 
     def decode_logits(self, bs):
         """the padded f32 [bs, Vpad] buffer every single-position step (either path) leaves its logits in: a dedicated tensor,
         so a captured decode graph and its sampler keep addressing the same memory"""
         return self.ws.get("dec_logits", (bs, self.Vpad), F32, exact=True)
+
+    def _decode_attend(self, cache, i, q, ctx, past, kv_len, pos_dev, pos_stride, qkv=None, **kw):
+        """Layer i's single-query step of a decode, on either cache layout (the one place the two part; a PagedKVCache's pages are
+        looked up through cache.table): with qkv, the RoPE + q / K-row / V^T-column write of the step's fused projection rows
+        (None: the QKV weight stream's epilogue wrote them), then the attention of q over the cache into ctx.  Returns what
+        ops.decode_attention returns; kw: its nsplit."""
+        w, bs, H, hd = self.w, q.shape[0], self.H, self.hd
+        if cache.paged:
+            if qkv is not None:
+                ops.qkv_split_paged(qkv, q, cache.k[i], cache.vt[i], cache.table, B=bs, H=H, hd=hd, cos=w["cos"], sin=w["sin"],
+                                    pos_dev=pos_dev, pos_stride=pos_stride)
+            return ops.decode_attention_paged(q, cache.k[i], cache.vt[i], ctx, cache.table, Smax=cache.smax, kv_len=kv_len,
+                                              pos_dev=pos_dev, pos_stride=pos_stride, **kw)
+        if qkv is not None:
+            ops.qkv_split(qkv, q, cache.k[i], cache.vt[i], B=bs, H=H, L=1, hd=hd, pos0=past, cos=w["cos"], sin=w["sin"],
+                          pos_dev=pos_dev, pos_stride=pos_stride)
+        return ops.decode_attention(q, cache.k[i], cache.vt[i], ctx, Smax=cache.smax if pos_dev is not None else past + 1,
+                                    q_pos0=past, kv_len=kv_len, pos_dev=pos_dev, pos_stride=pos_stride, **kw)
 
     def _decode_forward_wide(self, h, bs, cache, kv_len, pos_dev, pos_stride, past):
         """One new position per row for 9..64 rows (round 6: continuous batching past the 8-row streams).  Every weight matrix is
@@ -920,8 +941,6 @@ class LlamaEngine:
         RoPE + cache write, single-query attention, o-proj (+ residual), RMSNorm, gate/up (+ SwiGLU), down (+ residual); the norms are
         kernels of their own here (a 64-row operand no longer fits a workgroup's prologue).  Never-moved buffers: the step is captured."""
         w, ws, T, H, hd = self.w, self.ws, self.T, self.H, self.hd
-        dyn = pos_dev is not None
-        paged = getattr(cache, "paged", False)   # (PagedKVCache: pages looked up through cache.table)
         fp8 = w["fp8"]
         x = ws.get("decw_x", (bs, T), H16(), exact=True)
         qkv = ws.get("decw_qkv", (bs, 3 * T), H16(), exact=True)
@@ -932,39 +951,17 @@ class LlamaEngine:
         # straight from fp32 (gr_norm_fp8), a stored 16-bit activation through the row quantiser -- into never-moved buffers
         q8 = {K_: (ws.get(f"decw_q8_{K_}", (bs, K_), ops.FP8, exact=True), ws.get(f"decw_s8_{K_}", (bs,), F32, exact=True))
               for K_ in ((T, self.I) if fp8 else ())}
+        op = _Operands(fp8, self.eps, False, q8, x, tile=3)
 
-        def lin(h_f32, gain, wt, **kw):       # RMSNorm -> GEMM
-            if fp8:
-                x8, sx = ops.norm_fp8(h_f32, gain, None, self.eps, True, out=q8[T])
-                return ops.gemm(x8, wt[0], a_scale=sx, w_scale=wt[1], tile=3, **kw)
-            return ops.gemm(ops.rmsnorm(h_f32, gain, self.eps, out=x), wt[0], tile=3, **kw)
+        def attend(i, rows):
+            return self._decode_attend(cache, i, q, ctx, past, kv_len, pos_dev, pos_stride, qkv=rows, nsplit=1)
 
-        def lin16(a16, wt, **kw):             # stored 16-bit activation -> GEMM
-            if fp8:
-                x8, sx = ops.quant_rows_fp8(a16, out=q8[a16.shape[-1]])
-                return ops.gemm(x8, wt[0], a_scale=sx, w_scale=wt[1], tile=3, **kw)
-            return ops.gemm(a16, wt[0], tile=3, **kw)
-
-        for i, Lw in enumerate(w["layers"]):
-            lin(h, Lw["n1"], Lw["wqkv"], out=qkv)
-            if paged:
-                ops.qkv_split_paged(qkv, q, cache.k[i], cache.vt[i], cache.table, B=bs, H=H, hd=hd, cos=w["cos"], sin=w["sin"],
-                                    pos_dev=pos_dev, pos_stride=pos_stride)
-                ops.decode_attention_paged(q, cache.k[i], cache.vt[i], ctx, cache.table, Smax=cache.smax, kv_len=kv_len,
-                                           pos_dev=pos_dev, pos_stride=pos_stride, nsplit=1)
-            else:
-                ops.qkv_split(qkv, q, cache.k[i], cache.vt[i], B=bs, H=H, L=1, hd=hd, pos0=past, cos=w["cos"], sin=w["sin"],
-                              pos_dev=pos_dev, pos_stride=pos_stride)
-                ops.decode_attention(q, cache.k[i], cache.vt[i], ctx, Smax=cache.smax if dyn else past + 1, q_pos0=past,
-                                     kv_len=kv_len, pos_dev=pos_dev, pos_stride=pos_stride, nsplit=1)
-            lin16(ctx, Lw["wo"], resid=h, out=h, out_f32=True)
-            lin(h, Lw["n2"], Lw["wgu"], act=3, out=y)
-            lin16(y, Lw["wd"], resid=h, out=h, out_f32=True)
-        if not dyn:
+        self._layers(h, op, attend, qkv, y)
+        if pos_dev is None:
             cache.seq_len = past + 1
         logits = self.decode_logits(bs)
         if fp8 and "head8" in w:
-            lin(h, w["norm"], w["head8"], out_f32=True, out=logits)
+            op.norm_gemm(h, w["norm"], w["head8"], out_f32=True, out=logits)
             return logits.view(bs, 1, self.Vpad)[:, :, : self.V], None
         hn = ops.rmsnorm(h, w["norm"], self.eps, out=x)
         ops.gemm(hn, w["head"], out_f32=True, out=logits, tile=3)
@@ -975,8 +972,6 @@ class LlamaEngine:
         prologue builds its operand (RMSNorm of the fp32 residual rows / the merge of the attention's key slices) and whose
         epilogue is its consumer (RoPE + cache write, in-place residual update, SwiGLU): csrc/gemv_fused.hip."""
         w, ws, T, H, hd = self.w, self.ws, self.T, self.H, self.hd
-        dyn = pos_dev is not None
-        paged = getattr(cache, "paged", False)   # (PagedKVCache: pages looked up through cache.table)
         q = ws.get("dec_q", h16(bs, H, 1, hd), H16(), exact=True)
         ctx = ws.get("dec_ctx", h16(bs, T), H16(), exact=True)
         y = ws.get("dec_y", h16(bs, self.I), H16(), exact=True)
@@ -987,13 +982,8 @@ class LlamaEngine:
                 _trace("dec0.h_in", h)
             ops.gemv_fused(Lw["wqkv"][0], M=bs, norm=(h, Lw["n1"], self.eps), **ws8(Lw["wqkv"]),
                            qkv=dict(q=q, k=cache.k[i], vt=cache.vt[i], cos=w["cos"], sin=w["sin"], H=H, hd=hd, pos0=past,
-                                    pos_dev=pos_dev, pos_stride=pos_stride, **(dict(table=cache.table) if paged else {})))
-            if paged:
-                att = ops.decode_attention_paged(q, cache.k[i], cache.vt[i], ctx, cache.table, Smax=cache.smax, kv_len=kv_len,
-                                                 pos_dev=pos_dev, pos_stride=pos_stride)
-            else:
-                att = ops.decode_attention(q, cache.k[i], cache.vt[i], ctx, Smax=cache.smax if dyn else past + 1, q_pos0=past,
-                                           kv_len=kv_len, pos_dev=pos_dev, pos_stride=pos_stride)
+                                    pos_dev=pos_dev, pos_stride=pos_stride, table=cache.table))
+            att = self._decode_attend(cache, i, q, ctx, past, kv_len, pos_dev, pos_stride)
             if t0:
                 _trace("dec0.q", q)
                 TRACE["dec0.nsplit"] = att[1] if isinstance(att, tuple) else 1
@@ -1009,7 +999,7 @@ class LlamaEngine:
             if t0:
                 _trace("dec0.act", y)
             ops.gemv_fused(Lw["wd"][0], M=bs, x=y, resid=h, **ws8(Lw["wd"]))
-        if not dyn:
+        if pos_dev is None:
             cache.seq_len = past + 1
         if TRACE is not None and len(w["layers"]) == 1:
             _trace("dec.h_out", h)

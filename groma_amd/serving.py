@@ -270,30 +270,6 @@ class Request:
     hit: Optional["PrefixMatch"] = None     # prefix cache: the cached prefix this request's suffix prefill continues
 
 
-class _RowView:
-    """KVCache interface over the first `n` rows of a cache, so GromaModel.forward prefills straight into it."""
-
-    def __init__(self, arena, n):
-        self.k = [t[:n] for t in arena.k]
-        self.vt = [t[:n] for t in arena.vt]
-        self.bs, self.smax, self.seq_len, self.sp = n, arena.smax, 0, getattr(arena, "sp", 1)
-
-    def __len__(self):
-        return len(self.k)
-
-    def __getitem__(self, l):
-        S = self.seq_len
-        if self.sp == 2:  # reference-precision cache (engine.KVCache): the values the operand pairs stand for
-            return (ops.unsplit(self.k[l])[:, :, :S], ops.unsplit(self.vt[l])[:, :, :, :S].transpose(2, 3))
-        return (self.k[l][:, :, :S], self.vt[l][:, :, :, :S].transpose(2, 3))
-
-    def __bool__(self):
-        return True
-
-    def grow(self, smax):
-        raise RuntimeError("a KV slot cannot grow: the request exceeds max_len")
-
-
 class ContinuousBatcher:
     @engine.model_entry(lambda self, *a, **kw: (a[0] if a else kw["model"]).precision)
     def __init__(self, model, max_rows=8, max_len=1024, use_graph=True, grow_to=None, overlap_admission=None, admit_min=2, admit_hold=8,
@@ -419,7 +395,7 @@ class ContinuousBatcher:
         imgs = torch.stack([image] * k)
         def once():
             self.model.forward(input_ids=ids.clone(), images=imgs, use_cache=True, return_dict=True,
-                               _cache=_RowView(self.staging, k), _seeds=[0] * k)
+                               _cache=self.staging.rows(k), _seeds=[0] * k)
         # first pass EAGER: the workspace arenas grow to their working size and every kernel has had its first launch (lazy
         # function attributes, module load) -- a graph captured on this pass would be keyed on pre-growth addresses, never be
         # replayed, and sit in the LRU pools evicting useful ones.  Second pass: capture, on the settled addresses.
@@ -489,10 +465,9 @@ class ContinuousBatcher:
         try:
             staging = self.llm.new_cache(self.rows, new_len, dev)
             arena = self.llm.new_cache(self.rows, new_len, dev)
-            sp = getattr(arena, "sp", 1)
             for l in range(len(arena.k)):
                 arena.k[l][:, :, :old].copy_(self.arena.k[l])
-                arena.vt[l][..., : old * sp].copy_(self.arena.vt[l])
+                arena.vt[l][..., : old * arena.sp].copy_(self.arena.vt[l])
         except RuntimeError as e:   # (torch.cuda.OutOfMemoryError is a RuntimeError)
             staging = arena = None
             self._grow_failed_at = new_len       # do not retry this size for every over-long request of the queue
@@ -550,7 +525,7 @@ class ContinuousBatcher:
         empty = torch.zeros((0, 4))
         rb = [r.refer_boxes if r.refer_boxes is not None else empty for r in reqs] if any(r.refer_boxes is not None for r in reqs) else None
         gb = [r.ground_boxes if r.ground_boxes is not None else empty for r in reqs] if any(r.ground_boxes is not None for r in reqs) else None
-        view = _RowView(self.staging, k)
+        view = self.staging.rows(k)
         try:
             out = m.forward(input_ids=ids, images=torch.stack([r.image for r in reqs]), refer_boxes=rb, ground_boxes=gb,
                             use_cache=True, return_dict=True, output_hidden_states=True, _cache=view,
@@ -688,7 +663,7 @@ class ContinuousBatcher:
             # only the prefix the prompts fill (whole 64-position blocks: a prefix in the pair layout too): what lies behind a row's
             # position is rewritten by its own decode steps before it is ever attended to
             n = min(self.max_len, -(-max(r.prompt_len for r, _, _, _ in placed if r.slot is not None) // 64) * 64)
-            sp = getattr(self.arena, "sp", 1)
+            sp = self.arena.sp
             for l in range(len(self.arena.k)):
                 self.arena.k[l][:, :, :n].index_copy_(0, dst, self.staging.k[l][:, :, :n].index_select(0, src))
                 self.arena.vt[l][..., : n * sp].index_copy_(0, dst, self.staging.vt[l][..., : n * sp].index_select(0, src))

@@ -1,4 +1,4 @@
-"""A/B a python-side engine switch inside one gpurun call: python tests/diag/bench_flag.py Q_IN_PLACE=0 [bench args]"""
+"""A/B a python-side engine switch in one process: python tests/diag/bench_flag.py WIDE_DECODE=0 [bench args]"""
 import os, runpy, sys
 root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
 sys.path.insert(0, root)

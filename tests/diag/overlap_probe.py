@@ -5,7 +5,7 @@ import os, sys, threading, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from groma_amd import config, constants, engine, ops, synth
 from groma_amd.groma import GromaModel
-from groma_amd.serving import ContinuousBatcher, _RowView
+from groma_amd.serving import ContinuousBatcher
 
 rows = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 4
@@ -23,7 +23,7 @@ idsk = torch.stack([ids[i] for i in range(k)]).cpu()
 
 def prefill():
     with ops.precision(m.precision if isinstance(m.precision, str) and m.precision in ("bf16", "fp16", "ref") else "bf16"):
-        m.forward(input_ids=idsk.clone(), images=images, use_cache=True, return_dict=True, _cache=_RowView(b.staging, k), _seeds=list(range(k)))
+        m.forward(input_ids=idsk.clone(), images=images, use_cache=True, return_dict=True, _cache=b.staging.rows(k), _seeds=list(range(k)))
 
 
 HI = torch.cuda.Stream(priority=-1)   # the ticks' stream in the "priority" runs: its kernels are dispatched ahead of the prefill's
