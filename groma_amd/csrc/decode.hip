@@ -156,7 +156,7 @@ __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __
 #pragma unroll
   for (int o = TPD / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
   if (nsplit == 1) {
-    if (part == 0) out[(long)bh * HD + d] = f2bf(acc / denom);
+    if (part == 0) out[(long)bh * HD + d] = f2bf(denom > 0.f ? acc / denom : 0.f);  // no visible key: zeros, as attention_kernel
     return;
   }
   // ---- split keys: publish (un-normalised o, max, sum) of this slice; the o-proj GEMV merges the slices in slice

@@ -78,7 +78,8 @@ __device__ __forceinline__ bf16x8 gemv_merge8(const GemvFArgs& p, int m, int k0)
       for (int e = 0; e < 4; ++e) { o[e] += f * o0[e]; o[4 + e] += f * o1[e]; }
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) pk.u[e] = pack2bf(o[2 * e] / l, o[2 * e + 1] / l);
+    for (int e = 0; e < 4; ++e)  // (every slice empty -- the row has no visible key: zeros, as gr_decode_attention's nsplit = 1 output)
+      pk.u[e] = l > 0.f ? pack2bf(o[2 * e] / l, o[2 * e + 1] / l) : 0u;
   }
   return pk.v;
 }

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(GemmArgs p) {
           for (int e = 0; e < 4; ++e) { o[e] += f * o0[e]; o[4 + e] += f * o1[e]; }
         }
 #pragma unroll
-        for (int e = 0; e < 8; ++e) xv[m][e] = bf2f(f2bf(o[e] / l));
+        for (int e = 0; e < 8; ++e) xv[m][e] = l > 0.f ? bf2f(f2bf(o[e] / l)) : 0.f;  // (no visible key in any slice: zeros)
       } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e) xv[m][e] = 0.f;

@@ -171,7 +171,15 @@ int gr_rmsnorm(const float* x, const float* gamma, void* out, int rows, int C, l
  * counter, 1 = ragged per-row positions); Skv is then only the capacity bound that is validated.
  * q_ld > 0: q points at the fused projection buffer [B*Lq, q_ld] (row b*Lq+i, columns h*hd + d) and is read in place;
  * with rope_cos/rope_sin [pos, hd/2] HF rotate_half RoPE at position q_pos0 + i is applied while loading (the q copy
- * and its round trip that gr_qkv_split would make disappear: pass q = NULL there). */
+ * and its round trip that gr_qkv_split would make disappear: pass q = NULL there).
+ * Contract of the mask (tests/attn_cases.py, tests/test_attention_edges_gpu.py; the same for gr_attention_paged and the decode kernels):
+ *   - a query with NO visible key (kv_len[b] == 0) gets a row of zeros;
+ *   - a masked key has probability exactly 0, but the kernel still feeds the raw V^T bytes of every 64-key tile it reads to the MFMA
+ *     (P = 0 times them): K rows and V^T columns behind a row's limit, up to the end of the last tile some query of the row sees
+ *     (for V^T: up to kv_stride / the end of the page), must hold FINITE values -- whatever they are, they then cost nothing.  The
+ *     engine guarantees it: caches and page pools are allocated with zeros, growing zero-fills, and the 16-bit writers saturate
+ *     (tests/test_attn_cases.py::test_engine_caches_are_allocated_finite).  gr_decode_attention guards p > 0 itself and tolerates
+ *     non-finite bytes behind the limit. */
 int gr_attention_bf16(const void* q, const void* k, const void* vt, void* out, const int* kv_len, int B, int H, int Lq,
                       int Skv, int kv_stride, int head_dim, int causal, int q_pos0, float scale, const int* pos_dev,
                       int pos_stride, long q_ld, const float* rope_cos, const float* rope_sin, hipStream_t stream);
@@ -215,7 +223,8 @@ int gr_attention_paged(const void* q, const void* k_pool, const void* vt_pool, v
  *                          o-proj stream merges them while building its operand (gr_gemv_desc.a_parts, x_mode 2) -- no
  *                          cross-block hand-off inside the launch, hence no device-scope fence (an L2 write-back on a
  *                          multi-XCD part)
- * Position of row b = pos_dev ? pos_dev[b * pos_stride] : q_pos0 (see gr_attention_bf16). */
+ * Position of row b = pos_dev ? pos_dev[b * pos_stride] : q_pos0 (see gr_attention_bf16).  A row with no visible key
+ * (kv_len[b] == 0) gives zeros, from out and from the o-proj merge of its (all empty) slices alike. */
 int gr_decode_attention(const void* q, const void* k, const void* vt, void* out, const int* kv_len, int B, int H, int Smax,
                         int kv_stride, int head_dim, int q_pos0, float scale, const int* pos_dev, int pos_stride,
                         int nsplit, float* parts, hipStream_t stream);
