@@ -837,20 +837,13 @@ __device__ __forceinline__ float sample_uniform(long seed, int counter) {
   z ^= z >> 31;
   return (float)(z >> 40) * (1.0f / 16777216.0f);  // 24 bits -> [0, 1)
 }
-__global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restrict__ x, long* __restrict__ out, int V, long ld,
-                                                           const float* __restrict__ inv_temp, const long* __restrict__ seed,
-                                                           const int* __restrict__ pos, int pos_stride, int pos_off) {
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* xr = x + (long)row * ld;
-  const float it = inv_temp ? inv_temp[row] : 0.f;
-  __shared__ float sv[16];
-  __shared__ int si[16];
-  __shared__ int s_last, s_win;
-  const int chunk = (V + 1023) / 1024;
-  const int lo = min(V, tid * chunk), hi = min(V, lo + chunk);
-  // ---- max (and its first index: the greedy answer)
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
+// ---- device helpers shared by sample_rows_kernel and sample_rows_lp_kernel (one 1024-thread block per row, thread t owns the
+// contiguous chunk [lo, hi) of the vocabulary; sv / si: 16-entry LDS arrays of the block)
+// Row maximum and its first index, in every thread: chunk, wave butterfly, the 16 wave leaders through LDS.  Ends behind a barrier.
+__device__ __forceinline__ void row_max_first(const float* __restrict__ xr, int lo, int hi, float* sv, int* si, float& best, int& bi) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  best = -INFINITY;
+  bi = 0x7fffffff;
   auto take = [&](float v, int i) {
     if (v > best || (v == best && i < bi)) { best = v; bi = i; }
   };
@@ -862,18 +855,19 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
     take(ov, oi);
   }
   if (lane == 0) { sv[wave] = best; si[wave] = bi; }
-  if (tid == 0) { s_last = -1; s_win = 0x7fffffff; }
   __syncthreads();
-  for (int w = 0; w < 16; ++w) take(sv[w], si[w]);  // every thread now holds the row max
-  if (it == 0.f) {
-    if (tid == 0) out[row] = bi;
-    return;
-  }
-  const float m = best;
-  __syncthreads();  // sv is reused below
-  // ---- un-normalised probabilities: chunk sums, block exclusive scan (wave scan + sequential wave totals)
+  for (int w = 0; w < 16; ++w) take(sv[w], si[w]);
+}
+// un-normalised probability mass of the thread's chunk at inverse temperature `it`, summed in index order
+__device__ __forceinline__ float chunk_mass(const float* __restrict__ xr, int lo, int hi, float m, float it) {
   float local = 0.f;
   for (int i = lo; i < hi; ++i) local += __expf((xr[i] - m) * it);
+  return local;
+}
+// block exclusive scan of the chunk masses (wave scan, then the 16 wave totals in order) and their total.  Contains one barrier;
+// the caller keeps a barrier between the last read of sv and this call.
+__device__ __forceinline__ void block_scan_mass(float local, float* sv, float& excl, float& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float incl = local;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
@@ -881,18 +875,20 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
     if (lane >= o) incl += v;
   }
   if (lane == 63) sv[wave] = incl;
-  if (local > 0.f) atomicMax(&s_last, tid);
   __syncthreads();
-  float base = 0.f, total = 0.f;
+  float base = 0.f;
+  total = 0.f;
   for (int w = 0; w < 16; ++w) {
     if (w < wave) base += sv[w];
     total += sv[w];
   }
-  const float excl = base + incl - local;
-  const int counter = (pos ? pos[(long)row * pos_stride] : 0) + pos_off;
-  const float target = sample_uniform(seed ? seed[row] : 0, counter) * total;
-  // the owning chunk: excl <= target < excl + local; fp slack at the top end falls to the last chunk with mass
-  if (local > 0.f && excl <= target && (target < excl + local || tid == s_last)) {
+  excl = base + incl - local;
+}
+// the pick: the chunk that owns `target` (excl <= target < excl + local; fp slack at the top end falls to the last chunk with
+// mass, *s_last) walks its elements and posts the first index whose running mass passes the target
+__device__ __forceinline__ void pick_in_chunk(const float* __restrict__ xr, int lo, int hi, float m, float it, float local, float excl,
+                                              float target, const int* s_last, int* s_win) {
+  if (local > 0.f && excl <= target && (target < excl + local || (int)threadIdx.x == *s_last)) {
     float acc = excl;
     int pick = -1;
     for (int i = lo; i < hi; ++i) {
@@ -903,15 +899,205 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
         if (target < acc) break;
       }
     }
-    if (pick >= 0) atomicMin(&s_win, pick);
+    if (pick >= 0) atomicMin(s_win, pick);
   }
+}
+// the temperature draw of one row behind row_max_first (m = row maximum): leaves the winner in *s_win behind a barrier
+// (0x7fffffff: no element had mass -- the caller falls back to the arg-max)
+__device__ __forceinline__ void sample_row(const float* __restrict__ xr, int lo, int hi, float m, float it, long seed, int counter,
+                                           float* sv, int* s_last, int* s_win) {
+  const float local = chunk_mass(xr, lo, hi, m, it);
+  if (local > 0.f) atomicMax(s_last, (int)threadIdx.x);
+  float excl, total;
+  block_scan_mass(local, sv, excl, total);
+  const float target = sample_uniform(seed, counter) * total;
+  pick_in_chunk(xr, lo, hi, m, it, local, excl, target, s_last, s_win);
   __syncthreads();
+}
+
+__global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restrict__ x, long* __restrict__ out, int V, long ld,
+                                                           const float* __restrict__ inv_temp, const long* __restrict__ seed,
+                                                           const int* __restrict__ pos, int pos_stride, int pos_off) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* xr = x + (long)row * ld;
+  const float it = inv_temp ? inv_temp[row] : 0.f;
+  __shared__ float sv[16];
+  __shared__ int si[16];
+  __shared__ int s_last, s_win;
+  const int chunk = (V + 1023) / 1024;
+  const int lo = min(V, tid * chunk), hi = min(V, lo + chunk);
+  if (tid == 0) { s_last = -1; s_win = 0x7fffffff; }
+  // ---- max (and its first index: the greedy answer)
+  float best;
+  int bi;
+  row_max_first(xr, lo, hi, sv, si, best, bi);  // every thread now holds the row max
+  if (it == 0.f) {
+    if (tid == 0) out[row] = bi;
+    return;
+  }
+  __syncthreads();  // sv is reused below
+  const int counter = (pos ? pos[(long)row * pos_stride] : 0) + pos_off;
+  sample_row(xr, lo, hi, best, it, seed ? seed[row] : 0, counter, sv, &s_last, &s_win);
   if (tid == 0) out[row] = s_win != 0x7fffffff ? s_win : bi;
 }
 extern "C" int gr_sample_rows(const float* x, long* out, int rows, int V, long ld, const float* inv_temp, const long* seed,
                               const int* pos, int pos_stride, int pos_off, hipStream_t stream) {
   if (!x || !out || rows <= 0 || V <= 0 || pos_stride < 0) return GR_EINVAL;
   hipLaunchKernelGGL(sample_rows_kernel, dim3(rows), dim3(1024), 0, stream, x, out, V, ld, inv_temp, seed, pos, pos_stride, pos_off);
+  GR_CHECK_LAUNCH();
+  return GR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The sampler with per-token outputs (gr_sample_rows_lp, include/groma_hip.h): the token of sample_rows_kernel, bit for bit (the
+// helpers above, in the same order), plus
+//   logprob = (x[token] - m) - log(sum_j exp(x[j] - m))   m = row maximum; RAW logits (temperature 1) whatever the row samples at;
+//             the sum in block_scan_mass's order (chunk in index order, wave scan, 16 wave totals in order)
+//   top-k   = the k[row] first logits in (value descending, index ascending) order, ids and log-probabilities: every thread keeps
+//             the sorted 8 best of its chunk in registers, lists are merged pairwise (the 8 first of two sorted lists a, b are
+//             the bitonic sequence first(a[j], b[7 - j]); three compare-exchange stages sort it) along the wave butterfly, the 16
+//             wave lists go through LDS and wave 0 merges them the same way.  The order is total (indices are unique), so every
+//             lane of a butterfly ends with the same list.  No global atomics.
+//   scores  = the processed row (raw where inv_temp == 0, else x * inv_temp: HF's temperature warper) at slot *step of the arena
+// k[row] < 0: the row computes its token and nothing else (the work of sample_rows_kernel).
+__device__ __forceinline__ bool top_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
+__device__ __forceinline__ void top8_sort_bitonic(float (&v)[8], int (&ix)[8]) {
+#pragma unroll
+  for (int s = 4; s > 0; s >>= 1) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if ((j & s) == 0 && top_before(v[j + s], ix[j + s], v[j], ix[j])) {
+        const float tv = v[j]; v[j] = v[j + s]; v[j + s] = tv;
+        const int ti = ix[j]; ix[j] = ix[j + s]; ix[j + s] = ti;
+      }
+    }
+  }
+}
+__device__ __forceinline__ void top8_merge(float (&v)[8], int (&ix)[8], const float (&ov)[8], const int (&oi)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (top_before(ov[7 - j], oi[7 - j], v[j], ix[j])) { v[j] = ov[7 - j]; ix[j] = oi[7 - j]; }
+  top8_sort_bitonic(v, ix);
+}
+// one butterfly stage: merge with the list of lane ^ o
+__device__ __forceinline__ void top8_exchange(float (&v)[8], int (&ix)[8], int o) {
+  float ov[8];
+  int oi[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    ov[j] = __shfl_xor(v[j], o, 64);
+    oi[j] = __shfl_xor(ix[j], o, 64);
+  }
+  top8_merge(v, ix, ov, oi);
+}
+__global__ __launch_bounds__(1024) void sample_rows_lp_kernel(const float* __restrict__ x, long* __restrict__ out,
+                                                              float* __restrict__ logprob, int rows, int V, long ld,
+                                                              const float* __restrict__ inv_temp, const long* __restrict__ seed,
+                                                              const int* __restrict__ pos, int pos_stride, int pos_off,
+                                                              const int* __restrict__ k, int kmax, long* __restrict__ top_ids,
+                                                              float* __restrict__ top_lp, float* __restrict__ scores,
+                                                              const int* __restrict__ step, int score_steps, int lp_steps) {
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* xr = x + (long)row * ld;
+  const float it = inv_temp ? inv_temp[row] : 0.f;
+  const int kk = k ? min(k[row], kmax) : 0;
+  const int st = step ? *step : 0;
+  __shared__ float sv[16];
+  __shared__ int si[16];
+  __shared__ int s_last, s_win;
+  __shared__ float tv[16][8];
+  __shared__ int ti[16][8];
+  const int chunk = (V + 1023) / 1024;
+  const int lo = min(V, tid * chunk), hi = min(V, lo + chunk);
+  if (tid == 0) { s_last = -1; s_win = 0x7fffffff; }
+  // ---- the processed row (consecutive threads, consecutive elements: whole-line stores)
+  if (scores && st >= 0 && st < score_steps) {
+    float* dst = scores + ((long)st * rows + row) * V;
+    if (it == 0.f)
+      for (int i = tid; i < V; i += 1024) dst[i] = xr[i];
+    else
+      for (int i = tid; i < V; i += 1024) dst[i] = xr[i] * it;
+  }
+  // ---- the token, as sample_rows_kernel
+  float best;
+  int bi;
+  row_max_first(xr, lo, hi, sv, si, best, bi);
+  if (it == 0.f && kk < 0) {
+    if (tid == 0) out[row] = bi;
+    return;
+  }
+  __syncthreads();  // sv is reused below
+  int token = bi;
+  if (it != 0.f) {
+    const int counter = (pos ? pos[(long)row * pos_stride] : 0) + pos_off;
+    sample_row(xr, lo, hi, best, it, seed ? seed[row] : 0, counter, sv, &s_last, &s_win);
+    if (s_win != 0x7fffffff) token = s_win;
+  }
+  if (tid == 0) out[row] = token;
+  if (kk < 0) return;
+  const bool keep = lp_steps == 0 || (st >= 0 && st < lp_steps);  // a step beyond the arena writes nothing
+  const long slot = lp_steps == 0 ? row : (long)row * lp_steps + st;
+  // ---- log of the normaliser at temperature 1
+  float excl, total;
+  block_scan_mass(chunk_mass(xr, lo, hi, best, 1.f), sv, excl, total);
+  const float lse = logf(total);
+  if (tid == 0 && keep) logprob[slot] = ((unsigned)token < (unsigned)V ? xr[token] - best : NAN) - lse;  // (an all-NaN row has no token)
+  if (kmax == 0) return;
+  if (kk == 0) {  // no alternatives asked: the row's entries say so
+    if (tid < kmax && keep) { top_ids[slot * kmax + tid] = -1; top_lp[slot * kmax + tid] = -INFINITY; }
+    return;
+  }
+  // ---- the 8 first of the chunk, of the wave, of the block
+  float v[8];
+  int ix[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { v[j] = -INFINITY; ix[j] = 0x7fffffff; }
+  for (int i = lo; i < hi; ++i) {
+    float nv = xr[i];
+    int ni = i;
+    if (!top_before(nv, ni, v[7], ix[7])) continue;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (top_before(nv, ni, v[j], ix[j])) {
+        const float tvv = v[j]; v[j] = nv; nv = tvv;
+        const int tii = ix[j]; ix[j] = ni; ni = tii;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) top8_exchange(v, ix, o);
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { tv[wave][j] = v[j]; ti[wave][j] = ix[j]; }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    v[j] = lane < 16 ? tv[lane & 15][j] : -INFINITY;
+    ix[j] = lane < 16 ? ti[lane & 15][j] : 0x7fffffff;
+  }
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) top8_exchange(v, ix, o);
+  if (tid == 0 && keep) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (j < kmax) {
+        const bool on = j < kk && ix[j] != 0x7fffffff;
+        top_ids[slot * kmax + j] = on ? ix[j] : -1;
+        top_lp[slot * kmax + j] = on ? (v[j] - best) - lse : -INFINITY;
+      }
+    }
+  }
+}
+extern "C" int gr_sample_rows_lp(const float* x, long* out, float* logprob, int rows, int V, long ld, const float* inv_temp,
+                                 const long* seed, const int* pos, int pos_stride, int pos_off, const int* k, int kmax, long* top_ids,
+                                 float* top_lp, float* scores, const int* step, int score_steps, int lp_steps, hipStream_t stream) {
+  if (!x || !out || !logprob || rows <= 0 || V <= 0 || ld < V || pos_stride < 0) return GR_EINVAL;
+  if (kmax < 0 || kmax > 8 || (kmax > 0 && (!top_ids || !top_lp))) return GR_EINVAL;
+  if ((scores && score_steps <= 0) || lp_steps < 0 || (lp_steps > 0 && !step)) return GR_EINVAL;
+  hipLaunchKernelGGL(sample_rows_lp_kernel, dim3(rows), dim3(1024), 0, stream, x, out, logprob, rows, V, ld, inv_temp, seed, pos,
+                     pos_stride, pos_off, k, kmax, top_ids, top_lp, scores, step, score_steps, lp_steps);
   GR_CHECK_LAUNCH();
   return GR_OK;
 }

@@ -8,6 +8,7 @@ LlamaEngine      HF LlamaModel + heads, groma.py:389-402                       a
 Residual streams are fp32 in HBM; GEMM operands bf16 (fp32 accumulate); the proposer is fp32 end to end.
 """
 import collections
+import gc
 import copy
 import math
 
@@ -242,17 +243,26 @@ class GraphPool:
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(cur)
         err = None
-        with torch.cuda.stream(side):
-            g.capture_begin(capture_error_mode="thread_local")
-            try:
-                launch()
-            except BaseException as e:   # a launch that raises (GR_EINVAL, a workspace requested inside the capture) invalidates the capture
-                err = e
-            try:
-                g.capture_end()          # always end it: a dangling capture would poison every later launch on this stream
-            except Exception:
-                if err is None:
-                    raise
+        # no cyclic garbage collection inside the capture: a pass that starts between two launches may finalise a CUDAGraph (a dropped
+        # batcher's or decoder's), whose destructor synchronises the device on ROCm -- illegal while a stream captures, and an error
+        # thrown from a destructor aborts the process (seen once: an abort under "Garbage-collecting" with this frame on the stack)
+        gc_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.stream(side):
+                g.capture_begin(capture_error_mode="thread_local")
+                try:
+                    launch()
+                except BaseException as e:   # a launch that raises (GR_EINVAL, a workspace requested inside the capture) invalidates the capture
+                    err = e
+                try:
+                    g.capture_end()          # always end it: a dangling capture would poison every later launch on this stream
+                except Exception:
+                    if err is None:
+                        raise
+        finally:
+            if gc_on:
+                gc.enable()
         cur.wait_stream(side)            # (the streams are re-joined whatever happened)
         if err is not None:
             self._seen.pop(key, None)    # nothing is kept; the key starts counting again
@@ -1019,10 +1029,31 @@ class GreedyDecoder:
     every row appends at the same position past+1 (all-ones mask over the padded prefix); finished rows
     emit `pad`; the loop ends when every row has produced `eos`.  Nothing position-dependent is a kernel argument: the
     kernels read the step position from `pos` (gr_qkv_split / gr_attention_bf16 pos_dev), so the graph is replayed
-    unchanged for every token instead of ~330 launches per token going through the host."""
+    unchanged for every token instead of ~330 launches per token going through the host.
 
-    def __init__(self, llm, bs, smax, max_new, eos, pad, device):
+    outputs = (k, scores) asks for per-token outputs (None: none, and the step launches gr_sample_rows exactly as before): the
+    step's sampler is then gr_sample_rows_lp, which writes at the device step counter into `logprob` [bs, max_new] (natural-log
+    probability of every emitted token under softmax of the raw logits), with k in 1..8 the k best alternatives into `top_ids` /
+    `top_lp` [bs, max_new, 8] (entries k..7: id -1, -inf), and with scores=True the processed logits row (raw for greedy, logits /
+    temperature for sampling) into `scores` [max_new, bs, V].  The arenas describe what the SAMPLER chose: a finished row, which
+    emits `pad`, still has its slots written from its logits; generate() reports such a token's log-probability as 0.0 and hands
+    out the scores slot as the kernel wrote it."""
+
+    def __init__(self, llm, bs, smax, max_new, eos, pad, device, outputs=None):
         self.llm, self.bs, self.eos, self.pad = llm, bs, eos, pad
+        self.outputs = outputs
+        self.logprob = self.lp_k = self.top_ids = self.top_lp = self.scores = None
+        if outputs is not None:
+            k, scores = outputs
+            if k is not None and not 0 <= int(k) <= 8:
+                raise ValueError("output_logprobs must be in 0..8")
+            self.logprob = torch.zeros((bs, max_new), dtype=F32, device=device)
+            if k:
+                self.lp_k = torch.full((bs,), int(k), dtype=torch.int32, device=device)
+                self.top_ids = torch.full((bs, max_new, 8), -1, dtype=torch.int64, device=device)
+                self.top_lp = torch.full((bs, max_new, 8), float("-inf"), dtype=F32, device=device)
+            if scores:
+                self.scores = torch.zeros((max_new, bs, llm.V), dtype=F32, device=device)
         self.cache = llm.new_cache(bs, smax, device)
         I64, I32 = torch.int64, torch.int32
         self.tok = torch.zeros((bs,), dtype=I64, device=device)
@@ -1048,13 +1079,21 @@ class GreedyDecoder:
         ops.greedy_advance(self.nxt, self.tok, self.unfinished, self.seq, self.pos, self.step, self.n_unf,
                            eos=self.eos, pad=self.pad, inc_pos=inc_pos)
 
+    def _sample(self, logits, V, pos_off):
+        """next ids of `logits` into self.nxt; with outputs, also this step's slots of the arenas (step counter: self.step)"""
+        if self.outputs is None:
+            ops.sample_rows(logits, V, self.inv_temp, self.seed, pos=self.pos, pos_stride=0, pos_off=pos_off, out=self.nxt)
+        else:
+            ops.sample_rows_lp(logits, V, self.inv_temp, self.seed, pos=self.pos, pos_stride=0, pos_off=pos_off, out=self.nxt,
+                               logprob=self.logprob, k=self.lp_k, top_ids=self.top_ids, top_lp=self.top_lp, scores=self.scores,
+                               step=self.step)
+
     def _step(self):
         llm = self.llm
         ops.embed_gather(self.tok, llm.w["embed"], llm.w["new_embed"], out=self.h)
         llm.forward(self.h, self.bs, 1, self.cache, pos_dev=self.pos, pos_stride=0)
         # the token sampled from the logits at position `pos` sits at pos + 1 (pos_off = 1)
-        ops.sample_rows(llm.decode_logits(self.bs), llm.V, self.inv_temp, self.seed,
-                        pos=self.pos, pos_stride=0, pos_off=1, out=self.nxt)
+        self._sample(llm.decode_logits(self.bs), llm.V, 1)
         self._advance(1)
 
     def capture(self):
@@ -1081,8 +1120,7 @@ class GreedyDecoder:
         self.pos.fill_(L)
         self.step.zero_()
         self.unfinished.fill_(1)
-        ops.sample_rows(first_logits.contiguous(), first_logits.shape[-1], self.inv_temp, self.seed, pos=self.pos,
-                        pos_stride=0, pos_off=0, out=self.nxt)  # first new token: position L
+        self._sample(first_logits.contiguous(), first_logits.shape[-1], 0)  # first new token: position L
         self._advance(0)
         n = 1
         while n < max_new:

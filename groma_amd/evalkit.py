@@ -8,6 +8,8 @@ scaled to the image size).  Those scripts run unchanged on `groma_amd.groma.Grom
 This module is the same bookkeeping for a *batch* of images per GPU -- what the MI355X path is efficient at -- with one
 all-reduce of the three counters over RCCL.  Box maths is a few dozen floats per image: host side, as in the reference.
 """
+import math
+
 import torch
 
 
@@ -27,17 +29,36 @@ def pairwise_iou(a, b):
     return inter / (area_a[:, None] + area_b[None, :] - inter)
 
 
-def grounded_boxes(new_ids, pred_boxes, box_idx_token_ids):
-    """new_ids: generated ids of ONE image; pred_boxes [N,4] cxcywh in the order <r_j> indexes.  Returns the boxes the
-    answer points at, in generation order; ids that are not <r_k>, or k >= N, are dropped (eval_rec.py:106-108)."""
+def _grounded(new_ids, n_boxes, box_idx_token_ids):
+    """[(position in new_ids, k)] of the tokens <r_k> with k < n_boxes, in generation order"""
     first = box_idx_token_ids[0]
     n_tok = len(box_idx_token_ids)
     ks = [int(t) - first for t in new_ids.tolist()]
     if box_idx_token_ids != list(range(first, first + n_tok)):  # non-contiguous vocabulary: generic lookup
         table = {t: i for i, t in enumerate(box_idx_token_ids)}
         ks = [table.get(int(t), -1) for t in new_ids.tolist()]
-    ks = [k for k in ks if 0 <= k < n_tok and k < pred_boxes.shape[0]]
+    return [(j, k) for j, k in enumerate(ks) if 0 <= k < n_tok and k < n_boxes]
+
+
+def grounded_boxes(new_ids, pred_boxes, box_idx_token_ids):
+    """new_ids: generated ids of ONE image; pred_boxes [N,4] cxcywh in the order <r_j> indexes.  Returns the boxes the
+    answer points at, in generation order; ids that are not <r_k>, or k >= N, are dropped (eval_rec.py:106-108)."""
+    ks = [k for _, k in _grounded(new_ids, pred_boxes.shape[0], box_idx_token_ids)]
     return pred_boxes[ks] if ks else pred_boxes[:0]
+
+
+def grounded_scores(new_ids, logprobs, n_boxes, box_idx_token_ids):
+    """One confidence per box grounded_boxes returns, in the same order: exp(log-probability) of the region token that selected the
+    box (`logprobs`: one natural-log probability per entry of new_ids -- GenerateOutput.logprobs[i] or a served request's
+    `logprobs`).  A box selected by several tokens takes the FIRST one's value every time it appears."""
+    lp = [float(x) for x in (logprobs.tolist() if hasattr(logprobs, "tolist") else logprobs)]
+    if len(lp) != len(new_ids):
+        raise ValueError("logprobs must hold one entry per generated token")
+    first_lp = {}
+    sel = _grounded(new_ids, n_boxes, box_idx_token_ids)
+    for j, k in sel:
+        first_lp.setdefault(k, lp[j])
+    return [math.exp(first_lp[k]) for _, k in sel]
 
 
 class RecMeter:
@@ -49,17 +70,24 @@ class RecMeter:
         self.hits = 0.0
         self.invalid = 0.0
         self.count = 0.0
+        self.scores = []   # with logprobs: (confidence, IoU) of every image's recorded (first grounded) box; local to this process
 
-    def update(self, sequences, prompt_len, pred_boxes_list, gt_boxes_list, box_idx_token_ids):
-        """sequences [bs, P+new] (GenerateOutput.sequences); pred_boxes_list / gt_boxes_list: per-image cxcywh boxes"""
+    def update(self, sequences, prompt_len, pred_boxes_list, gt_boxes_list, box_idx_token_ids, logprobs=None):
+        """sequences [bs, P+new] (GenerateOutput.sequences); pred_boxes_list / gt_boxes_list: per-image cxcywh boxes.
+        logprobs [bs, new] (GenerateOutput.logprobs, optional): the box the meter scores is recorded in `scores` with the confidence
+        exp(log-probability of its region token); the counters do not depend on it."""
         for i in range(sequences.shape[0]):
             self.count += 1
             sel = grounded_boxes(sequences[i, prompt_len:].cpu(), pred_boxes_list[i].float().cpu(), box_idx_token_ids)
             if sel.shape[0] == 0:
                 self.invalid += 1
                 continue
+            if logprobs is not None:
+                conf = grounded_scores(sequences[i, prompt_len:].cpu(), logprobs[i], pred_boxes_list[i].shape[0], box_idx_token_ids)[0]
             ious = pairwise_iou(cxcywh_to_xyxy(sel), cxcywh_to_xyxy(gt_boxes_list[i].float().cpu())).max(dim=-1).values
             self.m_iou += float(ious[0])
+            if logprobs is not None:
+                self.scores.append((conf, float(ious[0])))
             self.hits += 1.0 if float(ious[0]) > self.threshold else 0.0
 
     def summary(self, device=None):
@@ -75,8 +103,10 @@ class RecMeter:
         return {f"iou@{self.threshold} accu": hits / n, "m_iou": miou / n, "missing percentage": invalid / n, "count": int(n)}
 
 
-def lvis_results(sequences, prompt_len, pred_boxes_list, img_ids, labels, img_shapes, box_idx_token_ids, label2cat=None):
-    """eval_lvis.py:147-166: every grounded box as an LVIS detection dict, xywh scaled to (h, w) of the image."""
+def lvis_results(sequences, prompt_len, pred_boxes_list, img_ids, labels, img_shapes, box_idx_token_ids, label2cat=None, logprobs=None):
+    """eval_lvis.py:147-166: every grounded box as an LVIS detection dict, xywh scaled to (h, w) of the image.  "score" is the
+    reference's constant 1.0 (eval_lvis.py:166), or -- with logprobs [bs, new] (GenerateOutput.logprobs) -- exp(log-probability) of the
+    region token that selected the box (grounded_scores)."""
     out = []
     for i in range(sequences.shape[0]):
         sel = grounded_boxes(sequences[i, prompt_len:].cpu(), pred_boxes_list[i].float().cpu(), box_idx_token_ids)
@@ -85,5 +115,7 @@ def lvis_results(sequences, prompt_len, pred_boxes_list, img_ids, labels, img_sh
         h, w = img_shapes[i]
         xywh = torch.stack([(sel[:, 0] - 0.5 * sel[:, 2]) * w, (sel[:, 1] - 0.5 * sel[:, 3]) * h, sel[:, 2] * w, sel[:, 3] * h], -1)
         cat = label2cat[labels[i]] if label2cat is not None else labels[i]
-        out += [{"image_id": img_ids[i], "category_id": cat, "bbox": b, "score": 1.0} for b in xywh.tolist()]
+        conf = [1.0] * sel.shape[0] if logprobs is None else \
+            grounded_scores(sequences[i, prompt_len:].cpu(), logprobs[i], pred_boxes_list[i].shape[0], box_idx_token_ids)
+        out += [{"image_id": img_ids[i], "category_id": cat, "bbox": b, "score": c} for b, c in zip(xywh.tolist(), conf)]
     return out

@@ -42,7 +42,18 @@ class CausalLMOutputWithPast(dict):
 
 
 class GenerateOutput(SimpleNamespace):
-    pass
+    """generate(return_dict_in_generate=True).  Per-token outputs, None unless asked for:
+    scores (output_scores=True): tuple of n tensors f32 [bs, vocab_size], the processed logits each token was chosen from (HF's
+      meaning: raw for greedy, logits / temperature when sampling);
+    logprobs (output_logprobs=k, k in 0..8) f32 [bs, n]: natural-log probability of each emitted token under softmax of the RAW
+      logits (temperature 1, comparable across temperatures; a temperature-scaled one is log_softmax(scores[i])); 0.0 for the pad
+      tokens of a finished row, whose scores / top_* entries are what the sampler saw;
+    top_logprobs / top_ids [bs, n, k] (k >= 1): the k largest raw logits, by value descending then token id ascending."""
+
+    def __init__(self, **kw):
+        for name in ("scores", "logprobs", "top_logprobs", "top_ids"):
+            kw.setdefault(name, None)
+        super().__init__(**kw)
 
 
 def _c2c(b):  # HF center_to_corners_format
@@ -758,20 +769,20 @@ class GromaModel:
         return torch.nn.utils.rnn.pad_sequence(new_labels, batch_first=True, padding_value=IGNORE_INDEX)
 
     # ------------------------------------------------------------------ hipGraph decode loop
-    def _decoder(self, bs, smax, max_new, eos, pad):
-        key = (bs, smax, max_new, eos, pad, self.gemm_plan)  # the plan is baked into the captured launches
+    def _decoder(self, bs, smax, max_new, eos, pad, outputs=None):
+        key = (bs, smax, max_new, eos, pad, self.gemm_plan, outputs)  # the plan and the sampler's outputs are baked into the captured launches
         pool = self.__dict__.setdefault("_decoders", {})
         dec = pool.get(key)
         if dec is None:
             if len(pool) >= 2:  # each arena owns a KV cache: keep the two most recent shapes
                 pool.pop(next(iter(pool)))
-            dec = engine.GreedyDecoder(self.llm, bs, smax, max_new, eos, pad, self.device)
+            dec = engine.GreedyDecoder(self.llm, bs, smax, max_new, eos, pad, self.device, outputs)
             dec.capture()  # before any prefill lands in the arena: the warm-up steps scribble on KV rows 0..2
             pool[key] = dec
         return dec
 
     def _generate_graph(self, seqs, ids, images, refer_boxes, ground_boxes, max_new_tokens, eos, pad, return_dict,
-                        output_hidden_states, temperature=0.0, draw_seeds=None):
+                        output_hidden_states, temperature=0.0, draw_seeds=None, outputs=None):
         """generate() with the per-token step captured once in a hipGraph (engine.GreedyDecoder): the step position,
         the token fed back, the finished mask and the output ids all live on the device, so one replay = one token
         and the host only reads the unfinished-row count when an EOS id is configured."""
@@ -780,7 +791,7 @@ class GromaModel:
         n_img_tok = (self.config.image_size // pc.vis_encoder_cfg.patch_size // 2) ** 2
         bound = P + n_img_tok + 2 * self.config.max_region_num + (sum(len(b) for b in refer_boxes) if refer_boxes else 0)
         smax = engine._ru(bound + max_new_tokens + 1, 256)
-        dec = self._decoder(bs, smax, engine._ru(max_new_tokens, 64), eos, pad)
+        dec = self._decoder(bs, smax, engine._ru(max_new_tokens, 64), eos, pad, outputs)
         first = self.forward(input_ids=ids, images=images, refer_boxes=refer_boxes, ground_boxes=ground_boxes,
                              use_cache=True, output_hidden_states=output_hidden_states, return_dict=True,
                              _last_logits_only=True, _reserve=max_new_tokens, _cache=dec.cache)
@@ -792,7 +803,28 @@ class GromaModel:
         if not return_dict:
             return seqs
         hs = (first.hidden_states,) if output_hidden_states else None
-        return GenerateOutput(sequences=seqs, hidden_states=hs, past_key_values=dec.cache)
+        extra = {}
+        if outputs is not None:  # copies: the arenas are rewritten by the next call
+            extra = self._token_outputs(outputs, dec.seq[:, :n], eos, dec.logprob[:, :n].clone(),
+                                        dec.top_ids[:, :n] if dec.top_ids is not None else None,
+                                        dec.top_lp[:, :n] if dec.top_lp is not None else None,
+                                        tuple(dec.scores[i].clone() for i in range(n)) if dec.scores is not None else None)
+        return GenerateOutput(sequences=seqs, hidden_states=hs, past_key_values=dec.cache, **extra)
+
+    @staticmethod
+    def _token_outputs(outputs, new_ids, eos, logprobs, top_ids, top_lp, scores):
+        """GenerateOutput's per-token fields from what the sampler wrote (logprobs [bs, n], top_* [bs, n, 8]); the pad tokens a
+        finished row emits report log-probability 0.0"""
+        k, _ = outputs
+        extra = {"scores": scores}
+        if k is not None:
+            if eos is not None:
+                done = ((new_ids == eos).cumsum(-1) - (new_ids == eos).long()) > 0   # positions behind a row's first EOS
+                logprobs = logprobs.masked_fill(done, 0.0)
+            extra["logprobs"] = logprobs
+            if k:
+                extra["top_ids"], extra["top_logprobs"] = top_ids[..., :k].clone(), top_lp[..., :k].clone()
+        return extra
 
     # ------------------------------------------------------------------ generate (HF 4.32 greedy_search semantics)
     @_entry
@@ -811,6 +843,14 @@ class GromaModel:
             do_sample = bool(getattr(gc, "do_sample", False))
         if kw.get("num_beams", 1) != 1:
             raise NotImplementedError("beam search is not implemented")
+        # per-token outputs (HF's output_scores; output_logprobs=k: each token's log-probability and the k best alternatives).  They
+        # travel in GenerateOutput, so they are produced only with return_dict_in_generate
+        lp_k = kw.get("output_logprobs")
+        if lp_k is not None and (isinstance(lp_k, bool) or int(lp_k) != lp_k or not 0 <= int(lp_k) <= 8):
+            raise ValueError("output_logprobs must be an integer in 0..8 (0: the chosen token only)")
+        outputs = (None if lp_k is None else int(lp_k), bool(kw.get("output_scores", False)))
+        if not return_dict_in_generate or outputs == (None, False):
+            outputs = None
         temperature = 0.0
         if do_sample:
             # the sampler the reference serves with (groma/serve/model_worker.py:307-311): softmax(logits / T) + multinomial;
@@ -832,7 +872,7 @@ class GromaModel:
         ids_for_model = input_ids.to(dev)
         if self.decode_graph and max_new_tokens > 1:
             return self._generate_graph(seqs, ids_for_model, images, refer_boxes, ground_boxes, max_new_tokens, eos, pad,
-                                        return_dict_in_generate, output_hidden_states, temperature, draw_seeds)
+                                        return_dict_in_generate, output_hidden_states, temperature, draw_seeds, outputs)
         out = self.forward(input_ids=ids_for_model, images=images, refer_boxes=refer_boxes, ground_boxes=ground_boxes,
                            use_cache=True, output_hidden_states=output_hidden_states, return_dict=True,
                            _last_logits_only=True, _reserve=max_new_tokens)
@@ -846,11 +886,24 @@ class GromaModel:
         seed_t = (seeds if seeds is not None else torch.zeros((bs,), dtype=I64)).to(dev)
         pos_t = torch.zeros((1,), dtype=I32, device=dev)
         L0 = cache.seq_len  # expanded prompt length: the first new token sits at position L0
+        lps, tids, tlps, scs = [], [], [], []
+        lp_kd = torch.full((bs,), outputs[0], dtype=I32, device=dev) if outputs is not None and outputs[0] else None
         for step in range(max_new_tokens):
             V = logits.shape[-1]
             last = logits[:, -1, :]
             pos_t.fill_(L0 + step)
-            nxt = ops.sample_rows(last if last.is_contiguous() else last.contiguous(), V, inv_t, seed_t, pos=pos_t)
+            last = last if last.is_contiguous() else last.contiguous()
+            if outputs is None:
+                nxt = ops.sample_rows(last, V, inv_t, seed_t, pos=pos_t)
+            else:  # the captured step's sampler (engine.GreedyDecoder._sample), one step's slots at a time
+                if lp_kd is not None:
+                    tids.append(torch.full((bs, 8), -1, dtype=I64, device=dev))
+                    tlps.append(torch.full((bs, 8), float("-inf"), dtype=F32, device=dev))
+                if outputs[1]:
+                    scs.append(torch.empty((1, bs, V), dtype=F32, device=dev))
+                nxt, lp = ops.sample_rows_lp(last, V, inv_t, seed_t, pos=pos_t, k=lp_kd, top_ids=tids[-1] if tids else None,
+                                             top_lp=tlps[-1] if tlps else None, scores=scs[-1] if scs else None)
+                lps.append(lp)
             if eos is not None:
                 nxt = nxt * unfinished + pad * (1 - unfinished)
             seqs = torch.cat([seqs, nxt[:, None]], dim=-1)
@@ -865,4 +918,9 @@ class GromaModel:
         if not return_dict_in_generate:
             return seqs
         hs = (first.hidden_states,) if output_hidden_states else None
-        return GenerateOutput(sequences=seqs, hidden_states=hs, past_key_values=cache)
+        extra = {}
+        if outputs is not None:
+            extra = self._token_outputs(outputs, seqs[:, input_ids.shape[1]:], eos, torch.stack(lps, dim=1),
+                                        torch.stack(tids, dim=1) if tids else None, torch.stack(tlps, dim=1) if tlps else None,
+                                        tuple(t[0] for t in scs) if scs else None)
+        return GenerateOutput(sequences=seqs, hidden_states=hs, past_key_values=cache, **extra)

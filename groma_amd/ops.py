@@ -737,6 +737,43 @@ def sample_rows(x, V, inv_temp, seed, pos=None, pos_stride=0, pos_off=0, out=Non
     return out
 
 
+def sample_rows_lp(x, V, inv_temp, seed, pos=None, pos_stride=0, pos_off=0, out=None, logprob=None, k=None, top_ids=None, top_lp=None,
+                   scores=None, step=None):
+    """sample_rows with per-token outputs (gr_sample_rows_lp, include/groma_hip.h): the same token ids, plus each token's natural-log
+    probability under softmax of the RAW logits (temperature 1) and, optionally, the k[row] (int32, 0..8) largest logits' ids /
+    log-probabilities in (value descending, index ascending) order and a copy of the processed row (raw where inv_temp == 0, else
+    x * inv_temp) into the arena scores f32 [steps, rows, V] at slot step[0].
+    logprob f32 [rows] with top_* [rows, kmax], or -- with the device step counter `step` -- arenas [rows, steps] / [rows, steps, kmax]
+    written at step[0].  Returns (ids, logprob)."""
+    lib = _lib.load()
+    _chk(x, F32, "x"); _chk(inv_temp, F32, "inv_temp"); _chk(seed, I64, "seed")
+    for t, dt, name in ((pos, I32, "pos"), (k, I32, "k"), (step, I32, "step"), (top_ids, I64, "top_ids"), (top_lp, F32, "top_lp"),
+                        (scores, F32, "scores"), (logprob, F32, "logprob")):
+        if t is not None:
+            _chk(t, dt, name)
+    rows = x.numel() // x.shape[-1]
+    if out is None:
+        out = torch.empty((rows,), dtype=I64, device=x.device)
+    if logprob is None:
+        logprob = torch.empty((rows,), dtype=F32, device=x.device)
+    lp_steps = logprob.shape[1] if logprob.dim() == 2 else 0
+    if logprob.shape[0] != rows or (k is not None and k.numel() != rows):
+        raise ValueError("logprob and k need one entry (row) per logits row")
+    if (top_ids is None) != (top_lp is None) or (top_ids is not None and top_ids.shape != top_lp.shape):
+        raise ValueError("top_ids and top_lp go together and share a shape")
+    kmax = 0
+    if top_ids is not None:
+        kmax = top_ids.shape[-1]
+        if tuple(top_ids.shape[:-1]) != tuple(logprob.shape):
+            raise ValueError("top_ids / top_lp must be logprob's shape + [kmax]")
+    if scores is not None and (scores.dim() != 3 or scores.shape[1] != rows or scores.shape[2] != V):
+        raise ValueError("scores must be [steps, rows, V]")
+    _lib.check(lib.gr_sample_rows_lp(_p(x), _p(out), _p(logprob), rows, V, x.shape[-1], _p(inv_temp), _p(seed), _p(pos), pos_stride,
+                                     pos_off, _p(k), kmax, _p(top_ids), _p(top_lp), _p(scores), _p(step),
+                                     scores.shape[0] if scores is not None else 0, lp_steps, _stream()), "gr_sample_rows_lp")
+    return out, logprob
+
+
 def greedy_advance(nxt, tok, unfinished, seq, pos, step, n_unfinished, *, eos, pad, inc_pos):
     """HF greedy_search bookkeeping of one step on the device (see include/groma_hip.h)"""
     lib = _lib.load()

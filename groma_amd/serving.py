@@ -268,6 +268,9 @@ class Request:
     error: Optional[str] = None
     pages: Optional[List[int]] = None       # paged mode: the pages reserved for this request (released when it finishes)
     hit: Optional["PrefixMatch"] = None     # prefix cache: the cached prefix this request's suffix prefill continues
+    logprobs_k: Optional[int] = None        # submit(logprobs=): None = off, 0 = each token's log-probability, 1..8 = plus that many alternatives
+    logprobs: Optional[List[float]] = None  # one per entry of `tokens` (natural log, softmax of the raw logits: temperature 1)
+    top_logprobs: Optional[List[List[tuple]]] = None   # logprobs_k >= 1: per token, the k best (token id, log-probability), best first
 
 
 class ContinuousBatcher:
@@ -332,7 +335,16 @@ class ContinuousBatcher:
         self.h = torch.zeros((max_rows, self.llm.T), dtype=F32, device=dev)
         self.inv_temp = torch.zeros((max_rows,), dtype=F32, device=dev)   # per-row 1/temperature (0 = greedy)
         self.seed = torch.zeros((max_rows,), dtype=I64, device=dev)       # per-row sampler seed
-        self.graph = None
+        # per-token log-probabilities (gr_sample_rows_lp): lp_k[row] = -1 (the row does not ask: its sampler work is gr_sample_rows'),
+        # 0 (the chosen token) or 1..8 (plus alternatives) -- device state, so rows that ask and rows that do not share one captured
+        # step.  The three outputs are views of ONE buffer: a tick on which a live row asked fetches it with one copy.
+        self.lp_k = torch.full((max_rows,), -1, dtype=I32, device=dev)
+        self._lp_pack = torch.zeros((max_rows * 100,), dtype=torch.uint8, device=dev)
+        self._lp_host = torch.zeros((max_rows * 100,), dtype=torch.uint8)
+        if torch.device(dev).type == "cuda":
+            self._lp_host = self._lp_host.pin_memory()
+        self.top_ids, self.top_lp, self.lp = self._lp_views(self._lp_pack)
+        self.graph = self.graph_lp = None
         self.steps = 0
         # overlapped admission: at most ONE prefill in flight (there is one staging cache), on `_side`; `_placed` orders the next
         # prefill's writes into the staging cache behind the previous batch's move into the arena
@@ -347,6 +359,11 @@ class ContinuousBatcher:
         self._job = None
         self._side = torch.cuda.Stream(device=dev) if self.overlap else None
         self._placed = None
+
+    def _lp_views(self, buf):
+        """(top_ids int64 [rows, 8], top_lp f32 [rows, 8], lp f32 [rows]) inside the log-probability buffer"""
+        n = self.rows
+        return buf[: n * 64].view(I64).view(n, 8), buf[n * 64: n * 96].view(F32).view(n, 8), buf[n * 96:].view(F32)
 
     @staticmethod
     def _check_paged(model, max_rows, max_len, grow_to, kv_pages):
@@ -407,39 +424,65 @@ class ContinuousBatcher:
 
     # ------------------------------------------------------------------ request intake
     def submit(self, input_ids, image, max_new_tokens=256, refer_boxes=None, ground_boxes=None, eos_token_id="config",
-               stop_token_id=None, seed=None, temperature=0.0):
+               stop_token_id=None, seed=None, temperature=0.0, logprobs=None):
+        """logprobs: None = off; 0 = `result(rid).logprobs` holds the natural-log probability of every returned token under softmax of
+        the raw logits (temperature 1, whatever the request samples at); 1..8 = `top_logprobs` also holds, per token, that many best
+        (token id, log-probability) pairs, by logit descending then id ascending."""
+        if logprobs is not None and (isinstance(logprobs, bool) or int(logprobs) != logprobs or not 0 <= int(logprobs) <= 8):
+            raise ValueError("logprobs must be None or an integer in 0..8")
         if eos_token_id == "config":
             eos_token_id = self.model.generation_config.eos_token_id
         r = Request(self._next_rid, input_ids.reshape(-1).to(I64).cpu(), image, int(max_new_tokens), refer_boxes, ground_boxes,
                     eos_token_id, stop_token_id, seed, float(temperature))
+        if logprobs is not None:
+            r.logprobs_k, r.logprobs = int(logprobs), []
+            if r.logprobs_k:
+                r.top_logprobs = []
         self._next_rid += 1
         self.queue.append(r)
         self.live[r.rid] = r
         return r.rid
 
     # ------------------------------------------------------------------ one decode step of every occupied row
-    def _decode(self):
+    def _decode(self, lp=False):
+        """lp: a live row asks for log-probabilities -- the sampler is gr_sample_rows_lp (rows that do not ask: lp_k = -1); else the
+        step is launch for launch what it was before that entry existed"""
         llm = self.llm
         ops.embed_gather(self.tok, llm.w["embed"], llm.w["new_embed"], out=self.h)
         llm.forward(self.h, self.rows, 1, self.arena, pos_dev=self.pos, pos_stride=1)
-        ops.sample_rows(llm.decode_logits(self.rows), llm.V, self.inv_temp, self.seed,
-                        pos=self.pos, pos_stride=1, pos_off=1, out=self.nxt)  # greedy rows: inv_temp 0 -> arg-max
+        self._sample(llm.decode_logits(self.rows), lp)
         ops.greedy_advance(self.nxt, self.tok, self.occupied, self._seq, self.pos, self.step_ctr, self.n_live,
                            eos=None, pad=0, inc_pos=2)
 
+    def _sample(self, logits, lp):
+        a = dict(pos=self.pos, pos_stride=1, pos_off=1, out=self.nxt)   # greedy rows: inv_temp 0 -> arg-max
+        if lp:
+            ops.sample_rows_lp(logits, self.llm.V, self.inv_temp, self.seed, logprob=self.lp, k=self.lp_k, top_ids=self.top_ids,
+                               top_lp=self.top_lp, **a)
+        else:
+            ops.sample_rows(logits, self.llm.V, self.inv_temp, self.seed, **a)
+
     def _capture(self):
-        """Capture the step once, before any request owns a slot (the warm-up steps write KV at the idle position)."""
+        """Capture the step once, before any request owns a slot (the warm-up steps write KV at the idle position): `graph`, and
+        `graph_lp`, the same step with the log-probability sampler, replayed on the ticks where a live row asks.  With every output off
+        that kernel measured 0.25 us (1.3 %) above sample_rows_kernel at 64 rows (profiles/r09_sampler_logprobs.txt), more than the
+        latter's run-to-run spread, so ticks on which nobody asks keep the plain step.  Both are captured here, never later: traffic
+        that mixes requests that ask with requests that do not only chooses between them."""
         side = torch.cuda.Stream(device=self.tok.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(3):
                 self._decode()
+            self._sample(self.llm.decode_logits(self.rows), True)   # (its first launch, outside a capture)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._decode()
-        self.graph = g
+        graphs = []
+        for lp in (False, True):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._decode(lp)
+            graphs.append(g)
+        self.graph, self.graph_lp = graphs
 
     # ------------------------------------------------------------------ KV arena growth
     def _bound(self, r):
@@ -564,11 +607,16 @@ class ContinuousBatcher:
         """(first token, 1/temperature) of a request from the logits of its last prompt position"""
         dev = self.tok.device
         it = 0.0 if r.temperature < 1e-4 else 1.0 / r.temperature
-        first = int(ops.sample_rows(logits_row[None].contiguous(), logits_row.shape[-1],
-                                    torch.tensor([it], dtype=F32, device=dev),
-                                    torch.tensor([int(r.seed or 0)], dtype=I64, device=dev),
-                                    pos=torch.tensor([r.prompt_len], dtype=I32, device=dev))[0])
-        return first, it
+        args = (logits_row[None].contiguous(), logits_row.shape[-1], torch.tensor([it], dtype=F32, device=dev),
+                torch.tensor([int(r.seed or 0)], dtype=I64, device=dev))
+        pos = torch.tensor([r.prompt_len], dtype=I32, device=dev)
+        if r.logprobs_k is None:
+            return int(ops.sample_rows(*args, pos=pos)[0]), it
+        # the first token's log-probability (and alternatives): the tick's sampler on this one row; kept on the request until _place emits it
+        top_ids, top_lp = torch.full((1, 8), -1, dtype=I64, device=dev), torch.full((1, 8), float("-inf"), dtype=F32, device=dev)
+        ids, lp = ops.sample_rows_lp(*args, pos=pos, k=torch.tensor([r.logprobs_k], dtype=I32, device=dev), top_ids=top_ids, top_lp=top_lp)
+        r._first_lp = (float(lp[0]), top_ids[0].tolist(), top_lp[0].tolist())
+        return int(ids[0]), it
 
     # ------------------------------------------------------------------ prefix cache
     def _keep_prefix(self, r, ids_x, emb):
@@ -642,7 +690,7 @@ class ContinuousBatcher:
         KV from the staging cache into the arena, arm the loop state."""
         rows, slots = [], []
         for r, i, first, it in placed:
-            self._emit(r, first)
+            self._emit(r, first, r.__dict__.pop("_first_lp", None))
             if r.done:
                 continue
             r.slot = self.slots.acquire(r.rid)
@@ -653,6 +701,7 @@ class ContinuousBatcher:
             self.occupied[r.slot] = 1
             self.inv_temp[r.slot] = it
             self.seed[r.slot] = int(r.seed or 0)
+            self.lp_k[r.slot] = -1 if r.logprobs_k is None else r.logprobs_k
         if self.paged:
             self._place_pages(reqs, placed, rows)
             return
@@ -820,8 +869,13 @@ class ContinuousBatcher:
             self._placed.record(torch.cuda.current_stream())
         return [(r.rid, r.tokens[-1] if r.tokens else None, r.done) for r in job["reqs"]]
 
-    def _emit(self, r, token):
+    def _emit(self, r, token, lp=None):
+        """lp: (log-probability, the 8 top ids, the 8 top log-probabilities) of `token`, for a request that asked"""
         r.tokens.append(token)
+        if r.logprobs_k is not None:
+            r.logprobs.append(lp[0])
+            if r.logprobs_k:
+                r.top_logprobs.append(list(zip(lp[1][: r.logprobs_k], lp[2][: r.logprobs_k])))
         if (r.eos_token_id is not None and token == r.eos_token_id) or \
                 (r.stop_token_id is not None and token == r.stop_token_id) or len(r.tokens) >= r.max_new_tokens:
             self._finish(r)
@@ -832,6 +886,7 @@ class ContinuousBatcher:
             s = r.slot
             self.occupied[s] = 0
             self.pos[s] = 0
+            self.lp_k[s] = -1
             if self.paged:
                 # the row's entries point at the sink page again (on the decode stream, so before any later _place can
                 # write these pages into another row's entries), then the pages go back to the pool
@@ -870,15 +925,22 @@ class ContinuousBatcher:
         act = self.slots.active()
         if not act:
             return events
+        # a tick on which a live row asked for log-probabilities runs the step with that sampler and queues ONE more copy
+        # (asynchronous, into pinned memory) in front of the ids' read, whose synchronisation covers it
+        ask = any(self.live[self.slots.owner[s]].logprobs_k is not None for s in act)
         if self.use_graph:
-            self.graph.replay()
+            (self.graph_lp if ask else self.graph).replay()
         else:
-            self._decode()
+            self._decode(ask)
         self.steps += 1
-        new = self.tok.tolist()  # the only per-step host read: max_rows ids
+        if ask:
+            self._lp_host.copy_(self._lp_pack, non_blocking=True)
+        new = self.tok.tolist()  # the only per-step synchronisation: max_rows ids
+        if ask:
+            top_ids, top_lp, lps = (t.tolist() for t in self._lp_views(self._lp_host))
         for s in act:
             r = self.live[self.slots.owner[s]]
-            self._emit(r, int(new[s]))
+            self._emit(r, int(new[s]), (lps[s], top_ids[s], top_lp[s]) if r.logprobs_k is not None else None)
             events.append((r.rid, r.tokens[-1], r.done))
         return events
 
@@ -906,7 +968,8 @@ class ContinuousBatcher:
     # ------------------------------------------------------------------ model_worker.generate_stream analogue
     def generate_stream(self, input_ids, image, max_new_tokens=256, stream_interval=1, **kw):
         """Yield the generated ids of ONE request every `stream_interval` tokens while other requests keep decoding
-        (groma/serve/model_worker.py:287-338 yields the decoded text; tokenisation stays with the caller)."""
+        (groma/serve/model_worker.py:287-338 yields the decoded text; tokenisation stays with the caller).  With logprobs=k (see
+        submit) every yield is (ids, logprobs, top_logprobs) instead, the lists aligned one to one (top_logprobs None for k = 0)."""
         rid = self.submit(input_ids, image, max_new_tokens=max_new_tokens, **kw)
         r = self.live[rid]
         sent = 0
@@ -916,5 +979,8 @@ class ContinuousBatcher:
                 raise RuntimeError(r.error)
             if len(r.tokens) - sent >= stream_interval or r.done:
                 sent = len(r.tokens)
-                yield list(r.tokens)
+                if r.logprobs_k is None:
+                    yield list(r.tokens)
+                else:
+                    yield list(r.tokens), list(r.logprobs), (list(r.top_logprobs) if r.logprobs_k else None)
         self.live.pop(rid, None)

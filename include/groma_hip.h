@@ -287,6 +287,25 @@ int gr_argmax_rows(const float* x, long* out, int rows, int V, long ld, hipStrea
  * replayable in a hipGraph, recomputable on the host). */
 int gr_sample_rows(const float* x, long* out, int rows, int V, long ld, const float* inv_temp, const long* seed,
                    const int* pos, int pos_stride, int pos_off, hipStream_t stream);
+/* gr_sample_rows with per-token outputs.  out[row] is gr_sample_rows' token for the same x, inv_temp, seed and position, bit for
+ * bit (arg-max ties: first maximal index; a draw that fp slack leaves unowned: the last chunk with mass).  In addition:
+ *   logprob  natural-log probability of that token under softmax of the RAW logits -- temperature 1 whatever inv_temp[row] is, so
+ *            values compare across requests that sample at different temperatures:
+ *              (x[token] - m) - log(sum_j exp(x[j] - m)),  m = the row maximum;
+ *            the sum runs in a fixed order (1024 contiguous chunks in index order, a wave scan, the 16 wave totals in order).
+ *   top-k    k[row] in 0..kmax alternatives (k NULL: 0): ids (int64) and log-probabilities (same definition) of the k[row]
+ *            largest logits, ordered by value descending, then index ascending among equals; entries k[row]..kmax-1 are id -1,
+ *            log-probability -inf.  kmax (0..8) is the row stride of top_ids / top_lp, which may be NULL when it is 0.
+ *            k[row] < 0: the row produces its token only (no logprob / top-k write): the work of gr_sample_rows.
+ *   scores   NULL = off; else the processed row as HF's `scores` holds it -- the raw row where inv_temp[row] == 0, x * inv_temp[row]
+ *            otherwise (a temperature-scaled distribution is log_softmax of that) -- copied to scores + (*step * rows + row) * V
+ *            when 0 <= *step < score_steps (step NULL: slot 0); a step beyond the arena writes nothing.
+ *   lp_steps 0: logprob [rows], top_* [rows, kmax].  > 0 (step required): logprob [rows, lp_steps] and top_* [rows, lp_steps, kmax]
+ *            are written at step *step, nothing when *step is beyond lp_steps.
+ * k, *step and the arenas are read on the device, so one captured launch serves any mixture of requests. */
+int gr_sample_rows_lp(const float* x, long* out, float* logprob, int rows, int V, long ld, const float* inv_temp, const long* seed,
+                      const int* pos, int pos_stride, int pos_off, const int* k, int kmax, long* top_ids, float* top_lp,
+                      float* scores, const int* step, int score_steps, int lp_steps, hipStream_t stream);
 /* one step of HF 4.32 GenerationMixin.greedy_search bookkeeping on the device (reference: the loop HF runs around
  * groma/model/groma.py:176-200): n = unfinished ? nxt : pad; seq[:, *step] = n; tok = n; unfinished &= n != eos;
  * ++*step; pos[0..pos_rows) += inc_pos; *n_unfinished = sum(unfinished).  eos < 0 = no stopping token.
