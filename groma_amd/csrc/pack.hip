@@ -426,10 +426,10 @@ __global__ void upsample_coord_kernel(const float* __restrict__ h, bf16_t* __res
     const f32x4 v11 = *(const f32x4*)(base + (long)(y1 * G + x1) * C);
     v = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
   } else if (c == C) {
-    // torch.linspace(-1, 1, n): start + i*step for the first half, end - (n-1-i)*step for the second
+    // torch.linspace(-1, 1, n): start + i*step for the first half, end - (n-1-i)*step for the second; n == 1 gives the start
     const float step = Ho > 1 ? 2.f / (float)(Ho - 1) : 0.f;
-    v[0] = x < Ho / 2 ? -1.f + step * x : 1.f - step * (Ho - 1 - x);
-    v[1] = y < Ho / 2 ? -1.f + step * y : 1.f - step * (Ho - 1 - y);
+    v[0] = (x < Ho / 2 || Ho == 1) ? -1.f + step * x : 1.f - step * (Ho - 1 - x);
+    v[1] = (y < Ho / 2 || Ho == 1) ? -1.f + step * y : 1.f - step * (Ho - 1 - y);
   }
   st4f(out, m * Cpad + c, v);
 }

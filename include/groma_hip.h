@@ -264,6 +264,14 @@ int gr_upsample_coord_pack(const float* h, void* out, int B, int G, int Ho, int 
 /* sums: f32 [imgs, gr_gn_stats_blocks(HW), C, 2] partials (no atomics: bit-reproducible) */
 int gr_gn_stats_blocks(int HW);
 int gr_gn_stats(const void* x, float* sums, int imgs, int HW, int C, hipStream_t stream);
+/* coef f32 [imgs, 2, C]: y = x * a[c] + b[c], a = rstd * gamma, b = beta - mean * a (torch.group_norm: biased variance, eps inside
+ * the square root).  The variance is the ONE-PASS sq / n - mean^2 in fp32, so its accuracy depends on the map's |mean| / std.
+ * Contract (tests/row_cases.py gn_bounds, checked per coefficient against float64): the relative error of a is at most
+ * C_GN * 2^-24 * (1 + mean^2 / (var + eps)) with C_GN = 15.6 (4 x the 3.9 an fp32 restatement of the two kernels measures), and b
+ * follows with one rounding more.  That is below 2^-12 -- a sixteenth of the unit roundoff of the bf16 map the coefficients are
+ * applied to -- for |mean| / std <= 16, and below a sixteenth of fp16's for |mean| / std <= 5.6: negligible for the region pyramid's
+ * conv outputs (|mean| / std of order 1).  A map with |mean| / std = 128 gets coefficients good to two digits; one that needs more
+ * must be centred before it comes here. */
 int gr_gn_finalize(const float* sums, const float* gamma, const float* beta, float* coef, int imgs, int HW, int C,
                    int groups, float eps, hipStream_t stream);
 int gr_fuse_shuffle(const void* tar, const float* tar_coef, int tarS, const void* top, const float* top_coef, int topS,
