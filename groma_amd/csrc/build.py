@@ -22,6 +22,7 @@ SOURCES = {
     "decode.hip": [],
     "norm.hip": [],
     "pack.hip": [],
+    "grammar.hip": [],
     "preprocess.hip": [],
     "ddetr.hip": [],
     # index-exact kernels: plain IEEE fp32 sequences, no FMA contraction (see oracle/roi_nms.c)

@@ -1037,11 +1037,21 @@ class GreedyDecoder:
     `top_lp` [bs, max_new, 8] (entries k..7: id -1, -inf), and with scores=True the processed logits row (raw for greedy, logits /
     temperature for sampling) into `scores` [max_new, bs, V].  The arenas describe what the SAMPLER chose: a finished row, which
     emits `pad`, still has its slots written from its logits; generate() reports such a token's log-probability as 0.0 and hands
-    out the scores slot as the kernel wrote it."""
+    out the scores slot as the kernel wrote it.
 
-    def __init__(self, llm, bs, smax, max_new, eos, pad, device, outputs=None):
+    grammar = a grammar.GrammarIds asks for grounded decoding (None: none, and the step launches what it launched before): the
+    captured step runs gr_grammar_step on the decode logits between the head and the sampler, on the device state `gstate` (per
+    row: -1 not constrained, 0 / 1 / 2 TEXT / OPEN / BODY) and `gn` (per row: the boxes of its image), so the sampler, and with
+    it every per-token output, sees -inf at the banned ids."""
+
+    def __init__(self, llm, bs, smax, max_new, eos, pad, device, outputs=None, grammar=None):
         self.llm, self.bs, self.eos, self.pad = llm, bs, eos, pad
         self.outputs = outputs
+        self.grammar = grammar
+        self.gstate = self.gn = None
+        if grammar is not None:
+            self.gstate = torch.full((bs,), -1, dtype=torch.int32, device=device)
+            self.gn = torch.zeros((bs,), dtype=torch.int32, device=device)
         self.logprob = self.lp_k = self.top_ids = self.top_lp = self.scores = None
         if outputs is not None:
             k, scores = outputs
@@ -1092,8 +1102,11 @@ class GreedyDecoder:
         llm = self.llm
         ops.embed_gather(self.tok, llm.w["embed"], llm.w["new_embed"], out=self.h)
         llm.forward(self.h, self.bs, 1, self.cache, pos_dev=self.pos, pos_stride=0)
+        logits = llm.decode_logits(self.bs)
+        if self.grammar is not None:
+            ops.grammar_step(logits, llm.V, self.gstate, self.gn, self.grammar, last_tok=self.tok)
         # the token sampled from the logits at position `pos` sits at pos + 1 (pos_off = 1)
-        self._sample(llm.decode_logits(self.bs), llm.V, 1)
+        self._sample(logits, llm.V, 1)
         self._advance(1)
 
     def capture(self):
@@ -1110,9 +1123,15 @@ class GreedyDecoder:
             self._step()
         self.graph = g
 
+    def set_grammar(self, grounded, n_boxes):
+        """grounded decoding, at the start of a call: row i starts in TEXT (grounded[i]) or unconstrained, with n_boxes[i] boxes"""
+        dev = self.gstate.device
+        self.gstate.copy_(torch.tensor([0 if g else -1 for g in grounded], dtype=torch.int32).to(dev))
+        self.gn.copy_(torch.tensor([int(n) for n in n_boxes], dtype=torch.int32).to(dev))
+
     def run(self, first_logits, L, max_new):
         """first_logits f32 [bs, V]: last-position logits of the prefill that filled cache[0:L).  Returns the number of
-        tokens produced; they are in self.seq[:, :n]."""
+        tokens produced; they are in self.seq[:, :n].  A grounded decoder masks a COPY of them (no token yet: the rows' start state)."""
         if max_new > self.seq.shape[1]:
             raise ValueError("max_new exceeds the arena")
         if self.graph is None:
@@ -1120,6 +1139,9 @@ class GreedyDecoder:
         self.pos.fill_(L)
         self.step.zero_()
         self.unfinished.fill_(1)
+        if self.grammar is not None:
+            first_logits = ops.grammar_step(first_logits.clone(memory_format=torch.contiguous_format), first_logits.shape[-1],
+                                            self.gstate, self.gn, self.grammar)
         self._sample(first_logits.contiguous(), first_logits.shape[-1], 0)  # first new token: position L
         self._advance(0)
         n = 1

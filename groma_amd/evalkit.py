@@ -61,8 +61,33 @@ def grounded_scores(new_ids, logprobs, n_boxes, box_idx_token_ids):
     return [math.exp(first_lp[k]) for _, k in sel]
 
 
+def region_lists(new_ids, box_idx_token_ids, bor, eor):
+    """The `[k, ...]` lists of an answer, one per `<roi>...</roi>` group in generation order: the indices k of the `<r_k>` between a
+    `bor` and the next `eor`.  A group that the answer's end cuts open is returned as it stands (its list may be empty); `<r_k>`
+    outside a group, and ids that are neither, are skipped.  Under grounded decoding (grammar.py) every list is non-empty, every k
+    is below the image's box count, and only the last one can be open."""
+    table = {int(t): i for i, t in enumerate(box_idx_token_ids)}
+    out, cur = [], None
+    for t in (new_ids.tolist() if hasattr(new_ids, "tolist") else new_ids):
+        t = int(t)
+        if t == bor:
+            if cur is not None:
+                out.append(cur)
+            cur = []
+        elif t == eor:
+            if cur is not None:
+                out.append(cur)
+            cur = None
+        elif cur is not None and t in table:
+            cur.append(table[t])
+    if cur is not None:
+        out.append(cur)
+    return out
+
+
 class RecMeter:
-    """Running REC counters of eval_rec.py:85-87,110-124; `summary` all-reduces them when a process group is up."""
+    """Running REC counters of eval_rec.py:85-87,110-124; `summary` all-reduces them when a process group is up.  Answers generated
+    with grounded=True (grammar.py) name only boxes the image has, so grounded_boxes drops no id of theirs."""
 
     def __init__(self, threshold=0.5):
         self.threshold = threshold
@@ -106,7 +131,8 @@ class RecMeter:
 def lvis_results(sequences, prompt_len, pred_boxes_list, img_ids, labels, img_shapes, box_idx_token_ids, label2cat=None, logprobs=None):
     """eval_lvis.py:147-166: every grounded box as an LVIS detection dict, xywh scaled to (h, w) of the image.  "score" is the
     reference's constant 1.0 (eval_lvis.py:166), or -- with logprobs [bs, new] (GenerateOutput.logprobs) -- exp(log-probability) of the
-    region token that selected the box (grounded_scores)."""
+    region token that selected the box (grounded_scores).  Under generate(grounded=True) (grammar.py) no `<r_k>` is dropped (every k
+    is below the image's box count) and that probability is over the image's own boxes."""
     out = []
     for i in range(sequences.shape[0]):
         sel = grounded_boxes(sequences[i, prompt_len:].cpu(), pred_boxes_list[i].float().cpu(), box_idx_token_ids)

@@ -21,7 +21,7 @@ from types import SimpleNamespace
 
 import torch
 
-from . import engine, ops, weights
+from . import engine, grammar, ops, weights
 from .config import GromaConfig
 from .constants import DEFAULT_TOKENS, REGION_IDX_TOKENS, IGNORE_INDEX
 
@@ -48,7 +48,10 @@ class GenerateOutput(SimpleNamespace):
     logprobs (output_logprobs=k, k in 0..8) f32 [bs, n]: natural-log probability of each emitted token under softmax of the RAW
       logits (temperature 1, comparable across temperatures; a temperature-scaled one is log_softmax(scores[i])); 0.0 for the pad
       tokens of a finished row, whose scores / top_* entries are what the sampler saw;
-    top_logprobs / top_ids [bs, n, k] (k >= 1): the k largest raw logits, by value descending then token id ascending."""
+    top_logprobs / top_ids [bs, n, k] (k >= 1): the k largest raw logits, by value descending then token id ascending.
+    Under generate(grounded=True) (grammar.py) the sampler runs behind the grammar mask, so for a grounded row `scores` carry -inf at
+    the banned ids (HF's meaning of processed scores under a logits processor), `logprobs` / `top_logprobs` are under the constrained
+    distribution -- behind `<roi>` a probability over the image's own boxes -- and alternatives past the allowed set report -inf."""
 
     def __init__(self, **kw):
         for name in ("scores", "logprobs", "top_logprobs", "top_ids"):
@@ -309,6 +312,9 @@ class GromaModel:
         self.refer_feat_token_id = tokenizer.convert_tokens_to_ids([DEFAULT_TOKENS['rfeat']])[0]
         self.ground_box_token_id = tokenizer.convert_tokens_to_ids([DEFAULT_TOKENS['gbox']])[0]
         self.box_idx_token_ids = tokenizer.convert_tokens_to_ids(REGION_IDX_TOKENS)
+        # <roi> / </roi>: the region-list brackets of the answer format (grounded decoding, grammar.py)
+        self.bor_token_id = tokenizer.convert_tokens_to_ids([DEFAULT_TOKENS['bor']])[0]
+        self.eor_token_id = tokenizer.convert_tokens_to_ids([DEFAULT_TOKENS['eor']])[0]
         self.generation_config.pad_token_id = tokenizer.pad_token_id
         return
 
@@ -769,20 +775,21 @@ class GromaModel:
         return torch.nn.utils.rnn.pad_sequence(new_labels, batch_first=True, padding_value=IGNORE_INDEX)
 
     # ------------------------------------------------------------------ hipGraph decode loop
-    def _decoder(self, bs, smax, max_new, eos, pad, outputs=None):
-        key = (bs, smax, max_new, eos, pad, self.gemm_plan, outputs)  # the plan and the sampler's outputs are baked into the captured launches
+    def _decoder(self, bs, smax, max_new, eos, pad, outputs=None, grammar=None):
+        # the plan, the sampler's outputs and the grammar step (its ids are launch arguments) are baked into the captured launches
+        key = (bs, smax, max_new, eos, pad, self.gemm_plan, outputs, grammar)
         pool = self.__dict__.setdefault("_decoders", {})
         dec = pool.get(key)
         if dec is None:
             if len(pool) >= 2:  # each arena owns a KV cache: keep the two most recent shapes
                 pool.pop(next(iter(pool)))
-            dec = engine.GreedyDecoder(self.llm, bs, smax, max_new, eos, pad, self.device, outputs)
+            dec = engine.GreedyDecoder(self.llm, bs, smax, max_new, eos, pad, self.device, outputs, grammar)
             dec.capture()  # before any prefill lands in the arena: the warm-up steps scribble on KV rows 0..2
             pool[key] = dec
         return dec
 
     def _generate_graph(self, seqs, ids, images, refer_boxes, ground_boxes, max_new_tokens, eos, pad, return_dict,
-                        output_hidden_states, temperature=0.0, draw_seeds=None, outputs=None):
+                        output_hidden_states, temperature=0.0, draw_seeds=None, outputs=None, grounded=None):
         """generate() with the per-token step captured once in a hipGraph (engine.GreedyDecoder): the step position,
         the token fed back, the finished mask and the output ids all live on the device, so one replay = one token
         and the host only reads the unfinished-row count when an EOS id is configured."""
@@ -791,12 +798,15 @@ class GromaModel:
         n_img_tok = (self.config.image_size // pc.vis_encoder_cfg.patch_size // 2) ** 2
         bound = P + n_img_tok + 2 * self.config.max_region_num + (sum(len(b) for b in refer_boxes) if refer_boxes else 0)
         smax = engine._ru(bound + max_new_tokens + 1, 256)
-        dec = self._decoder(bs, smax, engine._ru(max_new_tokens, 64), eos, pad, outputs)
+        gids = grammar.GrammarIds.from_model(self) if grounded is not None else None
+        dec = self._decoder(bs, smax, engine._ru(max_new_tokens, 64), eos, pad, outputs, gids)
         first = self.forward(input_ids=ids, images=images, refer_boxes=refer_boxes, ground_boxes=ground_boxes,
                              use_cache=True, output_hidden_states=output_hidden_states, return_dict=True,
                              _last_logits_only=True, _reserve=max_new_tokens, _cache=dec.cache)
         L = dec.cache.seq_len
         dec.set_sampling(temperature, draw_seeds() if draw_seeds is not None else None)
+        if grounded is not None:  # a row's box count: the rows of its image's pred_boxes, what its prompt was spliced with
+            dec.set_grammar(grounded, [b.shape[0] for b in first.hidden_states[1]["pred_boxes"]])
         n = dec.run(first.logits[:, -1, :], L, max_new_tokens)
         dec.cache.seq_len = L + n - 1
         seqs = torch.cat([seqs, dec.seq[:, :n]], dim=-1)
@@ -851,6 +861,18 @@ class GromaModel:
         outputs = (None if lp_k is None else int(lp_k), bool(kw.get("output_scores", False)))
         if not return_dict_in_generate or outputs == (None, False):
             outputs = None
+        # grounded decoding (grammar.py): True, or one bool per row; rows with False are not constrained.  None: nothing asked, and
+        # every launch is what it was
+        grounded = kw.get("grounded")
+        if grounded is not None and not isinstance(grounded, bool):
+            grounded = [bool(g) for g in grounded]
+            if len(grounded) != input_ids.shape[0]:
+                raise ValueError("grounded needs one entry per row")
+        elif grounded is not None:
+            grounded = [grounded] * input_ids.shape[0]
+        if grounded is not None and not any(grounded):
+            grounded = None
+        gids = grammar.GrammarIds.from_model(self) if grounded is not None else None
         temperature = 0.0
         if do_sample:
             # the sampler the reference serves with (groma/serve/model_worker.py:307-311): softmax(logits / T) + multinomial;
@@ -872,7 +894,7 @@ class GromaModel:
         ids_for_model = input_ids.to(dev)
         if self.decode_graph and max_new_tokens > 1:
             return self._generate_graph(seqs, ids_for_model, images, refer_boxes, ground_boxes, max_new_tokens, eos, pad,
-                                        return_dict_in_generate, output_hidden_states, temperature, draw_seeds, outputs)
+                                        return_dict_in_generate, output_hidden_states, temperature, draw_seeds, outputs, grounded)
         out = self.forward(input_ids=ids_for_model, images=images, refer_boxes=refer_boxes, ground_boxes=ground_boxes,
                            use_cache=True, output_hidden_states=output_hidden_states, return_dict=True,
                            _last_logits_only=True, _reserve=max_new_tokens)
@@ -888,11 +910,17 @@ class GromaModel:
         L0 = cache.seq_len  # expanded prompt length: the first new token sits at position L0
         lps, tids, tlps, scs = [], [], [], []
         lp_kd = torch.full((bs,), outputs[0], dtype=I32, device=dev) if outputs is not None and outputs[0] else None
+        if gids is not None:  # the captured step's grammar state (engine.GreedyDecoder.set_grammar)
+            g_state = torch.tensor([0 if g else -1 for g in grounded], dtype=I32).to(dev)
+            g_n = torch.tensor([b.shape[0] for b in first.hidden_states[1]["pred_boxes"]], dtype=I32).to(dev)
+        nxt = None
         for step in range(max_new_tokens):
             V = logits.shape[-1]
             last = logits[:, -1, :]
             pos_t.fill_(L0 + step)
             last = last if last.is_contiguous() else last.contiguous()
+            if gids is not None:  # on a copy: the prefill's logits are not ours to edit
+                last = ops.grammar_step(last.clone(), V, g_state, g_n, gids, last_tok=nxt)
             if outputs is None:
                 nxt = ops.sample_rows(last, V, inv_t, seed_t, pos=pos_t)
             else:  # the captured step's sampler (engine.GreedyDecoder._sample), one step's slots at a time

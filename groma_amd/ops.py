@@ -774,6 +774,23 @@ def sample_rows_lp(x, V, inv_temp, seed, pos=None, pos_stride=0, pos_off=0, out=
     return out, logprob
 
 
+def grammar_step(logits, V, state, n_boxes, ids, last_tok=None):
+    """Grounded decoding (gr_grammar_step, include/groma_hip.h): advance every row's grammar state (int32 [rows], -1 = row not
+    constrained) by its last token (int64 [rows]; None: no token yet) and write -inf over the ids the new state bans, in place, in
+    logits f32 [rows, ld] (columns V..ld untouched).  n_boxes int32 [rows]; ids: grammar.GrammarIds."""
+    lib = _lib.load()
+    _chk(logits, F32, "logits"); _chk(state, I32, "state"); _chk(n_boxes, I32, "n_boxes")
+    if last_tok is not None:
+        _chk(last_tok, I64, "last_tok")
+    rows = logits.numel() // logits.shape[-1]
+    if state.numel() != rows or n_boxes.numel() != rows or (last_tok is not None and last_tok.numel() != rows):
+        raise ValueError("state, n_boxes and last_tok need one entry per logits row")
+    never = (ctypes.c_long * max(1, len(ids.never)))(*ids.never)
+    _lib.check(lib.gr_grammar_step(_p(logits), rows, V, logits.shape[-1], _p(state), _p(last_tok), _p(n_boxes), ids.r_first,
+                                   ids.r_count, ids.bor, ids.eor, never, len(ids.never), _stream()), "gr_grammar_step")
+    return logits
+
+
 def greedy_advance(nxt, tok, unfinished, seq, pos, step, n_unfinished, *, eos, pad, inc_pos):
     """HF greedy_search bookkeeping of one step on the device (see include/groma_hip.h)"""
     lib = _lib.load()

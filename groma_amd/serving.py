@@ -44,7 +44,7 @@ from typing import List, Optional
 
 import torch
 
-from . import engine, ops
+from . import engine, grammar, ops
 
 I32, I64, F32 = torch.int32, torch.int64, torch.float32
 
@@ -271,17 +271,22 @@ class Request:
     logprobs_k: Optional[int] = None        # submit(logprobs=): None = off, 0 = each token's log-probability, 1..8 = plus that many alternatives
     logprobs: Optional[List[float]] = None  # one per entry of `tokens` (natural log, softmax of the raw logits: temperature 1)
     top_logprobs: Optional[List[List[tuple]]] = None   # logprobs_k >= 1: per token, the k best (token id, log-probability), best first
+    grounded: bool = False                  # submit(grounded=True): the region-token grammar (grammar.py) constrains every token
+    grammar_state: Optional[int] = None     # grounded, once done: the state behind the last token (1 / 2: cut inside a region list)
 
 
 class ContinuousBatcher:
     @engine.model_entry(lambda self, *a, **kw: (a[0] if a else kw["model"]).precision)
     def __init__(self, model, max_rows=8, max_len=1024, use_graph=True, grow_to=None, overlap_admission=None, admit_min=2, admit_hold=8,
-                 kv_pages=None, admit_rows=None, max_prompt_len=None, prefix_cache=False):
+                 kv_pages=None, admit_rows=None, max_prompt_len=None, prefix_cache=False, grounded=False):
         """kv_pages=N: a paged KV cache of N pages of 64 positions (engine.PagedKVCache) instead of max_rows slots of max_len positions;
         max_len is then the per-request cap.  admit_rows (default min(max_rows, 8)) bounds an admission wave, max_prompt_len (default
         min(max_len, 1024)) the prompt part of a request: the staging cache the prefills land in holds admit_rows x max_prompt_len.
         prefix_cache=True (paged mode only): requests with an explicit seed that share an image prefix with an earlier one map its
-        whole KV pages and prefill only their suffix (see `_take_batch` / `_prefill_hits`)."""
+        whole KV pages and prefill only their suffix (see `_take_batch` / `_prefill_hits`).
+        grounded=True: requests may ask for grounded decoding (submit(grounded=True), grammar.py).  The step is then also captured
+        with gr_grammar_step between the head and the sampler, on per-row device state (`gstate`: -1 = not constrained, `gn`: the
+        boxes of the row's image); those graphs are replayed on ticks where a live row is grounded, the plain ones otherwise."""
         if prefix_cache and kv_pages is None:
             raise ValueError("prefix_cache needs a paged KV cache (kv_pages=N): cached prefixes are shared as whole pages")
         if max_rows < 1 or max_rows > 64:
@@ -344,7 +349,14 @@ class ContinuousBatcher:
         if torch.device(dev).type == "cuda":
             self._lp_host = self._lp_host.pin_memory()
         self.top_ids, self.top_lp, self.lp = self._lp_views(self._lp_pack)
-        self.graph = self.graph_lp = None
+        # grounded decoding: the ids of the grammar (ValueError here when the model's do not describe it) and the per-row state
+        self.grounded = bool(grounded)
+        self.gids = self.gstate = self.gn = None
+        if self.grounded:
+            self.gids = grammar.GrammarIds.from_model(model)
+            self.gstate = torch.full((max_rows,), -1, dtype=I32, device=dev)
+            self.gn = torch.zeros((max_rows,), dtype=I32, device=dev)
+        self.graph = self.graph_lp = self.graph_g = self.graph_lp_g = None
         self.steps = 0
         # overlapped admission: at most ONE prefill in flight (there is one staging cache), on `_side`; `_placed` orders the next
         # prefill's writes into the staging cache behind the previous batch's move into the arena
@@ -424,16 +436,21 @@ class ContinuousBatcher:
 
     # ------------------------------------------------------------------ request intake
     def submit(self, input_ids, image, max_new_tokens=256, refer_boxes=None, ground_boxes=None, eos_token_id="config",
-               stop_token_id=None, seed=None, temperature=0.0, logprobs=None):
-        """logprobs: None = off; 0 = `result(rid).logprobs` holds the natural-log probability of every returned token under softmax of
+               stop_token_id=None, seed=None, temperature=0.0, logprobs=None, grounded=False):
+        """grounded=True (a batcher built with grounded=True): every token obeys the region-token grammar (grammar.py) with n = the
+        rows of the request's `pred_boxes`; `result(rid).grammar_state` is the state behind its last token.  The sampler runs behind
+        the mask, so `logprobs` / `top_logprobs` are under the constrained distribution and alternatives past the allowed set are -inf.
+        logprobs: None = off; 0 = `result(rid).logprobs` holds the natural-log probability of every returned token under softmax of
         the raw logits (temperature 1, whatever the request samples at); 1..8 = `top_logprobs` also holds, per token, that many best
         (token id, log-probability) pairs, by logit descending then id ascending."""
         if logprobs is not None and (isinstance(logprobs, bool) or int(logprobs) != logprobs or not 0 <= int(logprobs) <= 8):
             raise ValueError("logprobs must be None or an integer in 0..8")
+        if grounded and not self.grounded:
+            raise ValueError("submit(grounded=True) needs a batcher built with grounded=True (its grounded step is captured at construction)")
         if eos_token_id == "config":
             eos_token_id = self.model.generation_config.eos_token_id
         r = Request(self._next_rid, input_ids.reshape(-1).to(I64).cpu(), image, int(max_new_tokens), refer_boxes, ground_boxes,
-                    eos_token_id, stop_token_id, seed, float(temperature))
+                    eos_token_id, stop_token_id, seed, float(temperature), grounded=bool(grounded))
         if logprobs is not None:
             r.logprobs_k, r.logprobs = int(logprobs), []
             if r.logprobs_k:
@@ -444,13 +461,17 @@ class ContinuousBatcher:
         return r.rid
 
     # ------------------------------------------------------------------ one decode step of every occupied row
-    def _decode(self, lp=False):
+    def _decode(self, lp=False, gr=False):
         """lp: a live row asks for log-probabilities -- the sampler is gr_sample_rows_lp (rows that do not ask: lp_k = -1); else the
-        step is launch for launch what it was before that entry existed"""
+        step is launch for launch what it was before that entry existed.  gr: a live row is grounded -- gr_grammar_step masks the
+        logits in front of the sampler (rows that are not: gstate = -1, untouched)"""
         llm = self.llm
         ops.embed_gather(self.tok, llm.w["embed"], llm.w["new_embed"], out=self.h)
         llm.forward(self.h, self.rows, 1, self.arena, pos_dev=self.pos, pos_stride=1)
-        self._sample(llm.decode_logits(self.rows), lp)
+        logits = llm.decode_logits(self.rows)
+        if gr:
+            ops.grammar_step(logits, llm.V, self.gstate, self.gn, self.gids, last_tok=self.tok)
+        self._sample(logits, lp)
         ops.greedy_advance(self.nxt, self.tok, self.occupied, self._seq, self.pos, self.step_ctr, self.n_live,
                            eos=None, pad=0, inc_pos=2)
 
@@ -467,22 +488,28 @@ class ContinuousBatcher:
         `graph_lp`, the same step with the log-probability sampler, replayed on the ticks where a live row asks.  With every output off
         that kernel measured 0.25 us (1.3 %) above sample_rows_kernel at 64 rows (profiles/r09_sampler_logprobs.txt), more than the
         latter's run-to-run spread, so ticks on which nobody asks keep the plain step.  Both are captured here, never later: traffic
-        that mixes requests that ask with requests that do not only chooses between them."""
+        that mixes requests that ask with requests that do not only chooses between them.  A batcher built with grounded=True captures
+        the grounded variants of the two (`graph_g`, `graph_lp_g`) next to them, for the ticks on which a live row is grounded."""
         side = torch.cuda.Stream(device=self.tok.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(3):
                 self._decode()
             self._sample(self.llm.decode_logits(self.rows), True)   # (its first launch, outside a capture)
+            if self.grounded:   # (likewise; no token: no state changes, and what it writes is scratch the next step overwrites)
+                ops.grammar_step(self.llm.decode_logits(self.rows), self.llm.V, self.gstate, self.gn, self.gids)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         graphs = []
-        for lp in (False, True):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._decode(lp)
-            graphs.append(g)
-        self.graph, self.graph_lp = graphs
+        for gr in ((False, True) if self.grounded else (False,)):
+            for lp in (False, True):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._decode(lp, gr)
+                graphs.append(g)
+        self.graph, self.graph_lp = graphs[:2]
+        if self.grounded:
+            self.graph_g, self.graph_lp_g = graphs[2:]
 
     # ------------------------------------------------------------------ KV arena growth
     def _bound(self, r):
@@ -526,6 +553,7 @@ class ContinuousBatcher:
             # the three eager warm-up steps in front of a capture advance every row: keep the loop state aside and put it back (what they
             # wrote into live rows' KV lies at positions >= pos, which the next real step rewrites before it attends to them)
             keep = (self.tok, self.nxt, self.occupied, self.pos, self.step_ctr, self.n_live, self._seq, self.h)
+            keep += (self.gstate,) if self.grounded else ()
             saved = [t.clone() for t in keep]
             self.graph = None
             self._capture()
@@ -610,6 +638,11 @@ class ContinuousBatcher:
         args = (logits_row[None].contiguous(), logits_row.shape[-1], torch.tensor([it], dtype=F32, device=dev),
                 torch.tensor([int(r.seed or 0)], dtype=I64, device=dev))
         pos = torch.tensor([r.prompt_len], dtype=I32, device=dev)
+        if r.grounded:   # the tick's grammar step on this one row, in its start state (no token yet), on a copy of the prefill's logits
+            row = ops.grammar_step(logits_row[None].clone(memory_format=torch.contiguous_format), logits_row.shape[-1],
+                                   torch.zeros((1,), dtype=I32, device=dev),
+                                   torch.tensor([int(r.pred_boxes.shape[0])], dtype=I32, device=dev), self.gids)
+            args = (row,) + args[1:]
         if r.logprobs_k is None:
             return int(ops.sample_rows(*args, pos=pos)[0]), it
         # the first token's log-probability (and alternatives): the tick's sampler on this one row; kept on the request until _place emits it
@@ -702,6 +735,9 @@ class ContinuousBatcher:
             self.inv_temp[r.slot] = it
             self.seed[r.slot] = int(r.seed or 0)
             self.lp_k[r.slot] = -1 if r.logprobs_k is None else r.logprobs_k
+            if self.grounded:   # TEXT: the tick's kernel moves it on by `first`
+                self.gstate[r.slot] = 0 if r.grounded else -1
+                self.gn[r.slot] = int(r.pred_boxes.shape[0]) if r.grounded else 0
         if self.paged:
             self._place_pages(reqs, placed, rows)
             return
@@ -882,11 +918,15 @@ class ContinuousBatcher:
 
     def _finish(self, r):
         r.done = True
+        if r.grounded:
+            r.grammar_state = grammar.final_state(r.tokens, self.gids)
         if r.slot is not None:
             s = r.slot
             self.occupied[s] = 0
             self.pos[s] = 0
             self.lp_k[s] = -1
+            if self.grounded:
+                self.gstate[s] = -1
             if self.paged:
                 # the row's entries point at the sink page again (on the decode stream, so before any later _place can
                 # write these pages into another row's entries), then the pages go back to the pool
@@ -928,10 +968,14 @@ class ContinuousBatcher:
         # a tick on which a live row asked for log-probabilities runs the step with that sampler and queues ONE more copy
         # (asynchronous, into pinned memory) in front of the ids' read, whose synchronisation covers it
         ask = any(self.live[self.slots.owner[s]].logprobs_k is not None for s in act)
+        gr = self.grounded and any(self.live[self.slots.owner[s]].grounded for s in act)
         if self.use_graph:
-            (self.graph_lp if ask else self.graph).replay()
+            if gr:
+                (self.graph_lp_g if ask else self.graph_g).replay()
+            else:
+                (self.graph_lp if ask else self.graph).replay()
         else:
-            self._decode(ask)
+            self._decode(ask, gr)
         self.steps += 1
         if ask:
             self._lp_host.copy_(self._lp_pack, non_blocking=True)
@@ -968,7 +1012,8 @@ class ContinuousBatcher:
     # ------------------------------------------------------------------ model_worker.generate_stream analogue
     def generate_stream(self, input_ids, image, max_new_tokens=256, stream_interval=1, **kw):
         """Yield the generated ids of ONE request every `stream_interval` tokens while other requests keep decoding
-        (groma/serve/model_worker.py:287-338 yields the decoded text; tokenisation stays with the caller).  With logprobs=k (see
+        (groma/serve/model_worker.py:287-338 yields the decoded text; tokenisation stays with the caller).  Keywords go to submit()
+        (grounded=True: the yielded ids obey the region-token grammar).  With logprobs=k (see
         submit) every yield is (ids, logprobs, top_logprobs) instead, the lists aligned one to one (top_logprobs None for k = 0)."""
         rid = self.submit(input_ids, image, max_new_tokens=max_new_tokens, **kw)
         r = self.live[rid]

@@ -314,6 +314,20 @@ int gr_sample_rows(const float* x, long* out, int rows, int V, long ld, const fl
 int gr_sample_rows_lp(const float* x, long* out, float* logprob, int rows, int V, long ld, const float* inv_temp, const long* seed,
                       const int* pos, int pos_stride, int pos_off, const int* k, int kmax, long* top_ids, float* top_lp,
                       float* scores, const int* step, int score_steps, int lp_steps, hipStream_t stream);
+/* grounded decoding: one step of the region-token grammar of `<roi><r_k>...</roi>` on the logits a sampler is about to read
+ * (csrc/grammar.hip; the host statement is groma_amd/grammar.py).  One workgroup per row.  A row with state[row] < 0 is not
+ * touched.  Otherwise the transition for last_tok[row] is applied and stored (bor -> 1, an id of R = [r_first, r_first +
+ * r_count) -> 2, eor -> 0, anything else, or last_tok NULL = no token yet, leaves it), and -inf is written over the banned
+ * entries of logits[row, 0:V), with n = n_boxes[row] clamped to 0..r_count:
+ *   0 TEXT: all of R, eor, the `never` ids, and bor when n == 0 (these <= r_count + 2 + n_never elements only);
+ *   1 OPEN: everything except r_first .. r_first+n-1 (n == 0: everything except eor);
+ *   2 BODY: everything except r_first .. r_first+n-1 and eor.
+ * Allowed entries and columns V..ld are neither read nor written.  logits, state, last_tok and n_boxes are device memory, so one
+ * captured launch serves any mix of rows and states; `never` (n_never <= 8 ids) is HOST memory, read before the launch.
+ * EINVAL before any launch: NULL logits / state / n_boxes, rows <= 0, V <= 0, ld < V, r_count < 0, n_never > 8 (or > 0 with
+ * never NULL), R, bor, eor or a never id outside [0, V), bor == eor, bor or eor inside R. */
+int gr_grammar_step(float* logits, int rows, int V, long ld, int* state, const long* last_tok, const int* n_boxes,
+                    long r_first, int r_count, long bor, long eor, const long* never, int n_never, hipStream_t stream);
 /* one step of HF 4.32 GenerationMixin.greedy_search bookkeeping on the device (reference: the loop HF runs around
  * groma/model/groma.py:176-200): n = unfinished ? nxt : pad; seq[:, *step] = n; tok = n; unfinished &= n != eos;
  * ++*step; pos[0..pos_rows) += inc_pos; *n_unfinished = sum(unfinished).  eos < 0 = no stopping token.
