@@ -98,6 +98,8 @@ SIGNATURES = {
     "gr_sample_rows": [_P, _P, _I, _I, _L, _P, _P, _P, _I, _I, _P],
     "gr_sample_rows_lp": [_P, _P, _P, _I, _I, _L, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P],
     "gr_grammar_step": [_P, _I, _I, _L, _P, _P, _P, _L, _I, _L, _L, _P, _I, _P],
+    "gr_label_logprob_rows": [_P, _I, _I, _L, _P, _P, _P, _P, _P, _P],
+    "gr_gather_rows_f32": [_P, _P, _P, _L, _I, _L, _P],
     "gr_greedy_advance": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _I, _I, _I, _P],
     "gr_msda_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "gr_mha32_f32": [_P, _P, _P, _I, _I, _I, _I, _F, _P],

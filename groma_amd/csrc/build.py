@@ -23,6 +23,8 @@ SOURCES = {
     "norm.hip": [],
     "pack.hip": [],
     "grammar.hip": [],
+    # the scoring reduction: one rounding per written operation, so the float32 restatement of its order is exact about it
+    "score.hip": ["-ffp-contract=off"],
     "preprocess.hip": [],
     "ddetr.hip": [],
     # index-exact kernels: plain IEEE fp32 sequences, no FMA contraction (see oracle/roi_nms.c)

@@ -11,6 +11,7 @@ import collections
 import gc
 import copy
 import math
+from types import SimpleNamespace
 
 import torch
 
@@ -754,8 +755,10 @@ class LlamaEngine:
             return "wide"
         return None
 
-    def forward(self, h, bs, L, cache, kv_len=None, all_logits=True, pos_dev=None, pos_stride=0, states=None):
+    def forward(self, h, bs, L, cache, kv_len=None, all_logits=True, pos_dev=None, pos_stride=0, states=None, head_rows=None):
         """h: f32 [bs*L, T] input embeddings (consumed as the residual stream, updated in place).
+        head_rows: (rows i32 [n], targets i64 [n], chunk, return_logits) -- a prefill whose head runs on those flat rows of the
+        residual stream only and scores each against its target (_head_rows, whose result is returned instead of the logits).
         states: a list that receives a copy of the residual stream in front of every layer (HF `all_hidden_states`, R:
         groma/model/groma.py:389-397 with output_hidden_states=True); the launches then run eagerly.
         Appends L positions to `cache`.  Returns logits f32 [bs, L or 1, V] (view into a Vpad-wide buffer).
@@ -767,6 +770,8 @@ class LlamaEngine:
         dyn = pos_dev is not None
         past = 0 if dyn else cache.seq_len
         path = self.decode_path(M, cache.smax, L, states)
+        if head_rows is not None and (path is not None or dyn or cache.paged):
+            raise ValueError("head_rows belongs to a prefill on the general kernels (L > 1, host positions, a slot KV cache)")
         if cache.paged and (path is None or not dyn or bs > cache.bs):
             # the general kernels (and every L > 1 path) address a slot arena: never hand them the pools of a paged cache
             raise ValueError("a paged KV cache is read and written only by the decode step of the weight-streaming kernels "
@@ -828,6 +833,8 @@ class LlamaEngine:
         if not dyn:
             cache.seq_len = past + L
         with st("head"):
+            if head_rows is not None:
+                return self._head_rows(h, *head_rows)
             return self._head(h, bs, L, xh_b, all_logits)
 
     def _layers(self, h, op, attend, qkv_b, y_b, x2_b=None, trace=False, states=None, L=1):
@@ -889,6 +896,39 @@ class LlamaEngine:
         # recycled arena view (the caching allocator re-serves the block once the caller drops the previous result)
         logits = ops.gemm(hn, w["head"], out_f32=True)
         return logits.view(bs, L, self.Vpad)[:, :, : self.V], hn
+
+    def _head_rows(self, h, rows, targets, chunk, return_logits=False):
+        """The head over chosen rows only (GromaModel.score): rows (i32 [n], device) are flat rows of the residual stream h, targets
+        (i64 [n]) the label each is scored against.  At most `chunk` rows at a time are gathered, normalised (final RMSNorm) and
+        multiplied by the head under the head stage's operand type -- the e4m3 head and the operand-pair build form their operands as
+        _head does -- into ONE recycled [chunk, Vpad] logits buffer, which gr_label_logprob_rows reduces before the next chunk
+        overwrites it: the [bs * L, Vpad] logits of a full head are never allocated.  Returns a namespace of [n] tensors logprob (f32),
+        greedy (i64), rank (i32), and logits f32 [n, V] (a copy of the scored rows) with return_logits, else None."""
+        w, ws, T, dev = self.w, self.ws, self.T, h.device
+        n = rows.numel()
+        chunk = max(1, min(int(chunk), n))
+        out = SimpleNamespace(logprob=torch.empty((n,), dtype=F32, device=dev), greedy=torch.empty((n,), dtype=I64, device=dev),
+                              rank=torch.empty((n,), dtype=I32, device=dev),
+                              logits=torch.empty((n, self.V), dtype=F32, device=dev) if return_logits else None)
+        head8 = w["fp8"] and "head8" in w
+        hs_b, lg_b = ws.get("score_h", (chunk, T), F32), ws.get("score_logits", (chunk, self.Vpad), F32)
+        if head8:
+            q_b, s_b = ws.get("score_q8", (chunk, T), ops.FP8), ws.get("score_s8", (chunk,), F32)
+        else:
+            x_b = ws.get("score_x", h16(chunk, T), H16())
+        for c0 in range(0, n, chunk):
+            m = min(chunk, n - c0)
+            hs, lg = ops.gather_rows(h, rows[c0: c0 + m], out=hs_b[:m]), lg_b[:m]
+            if head8:
+                x8, sx = ops.norm_fp8(hs, w["norm"], None, self.eps, True, out=(q_b[:m], s_b[:m]))
+                ops.gemm(x8, w["head8"][0], a_scale=sx, w_scale=w["head8"][1], out_f32=True, out=lg)
+            else:
+                ops.gemm(ops.rmsnorm(hs, w["norm"], self.eps, out=x_b[:m]), w["head"], out_f32=True, out=lg)
+            ops.label_logprob_rows(lg, self.V, targets[c0: c0 + m], out=out.logprob[c0: c0 + m], greedy=out.greedy[c0: c0 + m],
+                                   rank=out.rank[c0: c0 + m])
+            if return_logits:
+                out.logits[c0: c0 + m].copy_(lg[:, : self.V])
+        return out
 
     def prefill_paged(self, h, bs, Lq, cache, table, pos_dev, kv_len=None):
         """Prefill continuation on a PagedKVCache (the continuous batcher's prefix-cache hits): h f32 [bs*Lq, T] holds the input rows

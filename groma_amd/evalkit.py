@@ -85,6 +85,29 @@ def region_lists(new_ids, box_idx_token_ids, bor, eor):
     return out
 
 
+def rank_choices(sequence_logprob, num_tokens, groups, length_normalize=False):
+    """Likelihood ranking of candidate answers (multiple choice): sequence_logprob / num_tokens are ScoreOutput's per-row values,
+    groups a list of lists of row indices (the candidates of one question).  Returns, per group, the position INSIDE the group of
+    the candidate with the largest summed log-probability -- per scored token with length_normalize.  Ties go to the first
+    candidate.  A candidate with no scored token (its sum of 0 would beat every real answer) or a NaN score ranks as -inf; a group
+    of nothing else answers 0.  Host only."""
+    lp = [float(x) for x in (sequence_logprob.tolist() if hasattr(sequence_logprob, "tolist") else sequence_logprob)]
+    nt = [int(x) for x in (num_tokens.tolist() if hasattr(num_tokens, "tolist") else num_tokens)]
+    if len(lp) != len(nt):
+        raise ValueError("sequence_logprob and num_tokens need one entry per row")
+    picks = []
+    for g in groups:
+        if len(g) == 0:
+            raise ValueError("a group needs at least one candidate row")
+        best, best_v = 0, -math.inf
+        for j, r in enumerate(g):
+            v = -math.inf if nt[r] <= 0 or lp[r] != lp[r] else (lp[r] / nt[r] if length_normalize else lp[r])
+            if v > best_v:
+                best, best_v = j, v
+        picks.append(best)
+    return picks
+
+
 class RecMeter:
     """Running REC counters of eval_rec.py:85-87,110-124; `summary` all-reduces them when a process group is up.  Answers generated
     with grounded=True (grammar.py) name only boxes the image has, so grounded_boxes drops no id of theirs."""

@@ -21,7 +21,7 @@ from types import SimpleNamespace
 
 import torch
 
-from . import engine, grammar, ops, weights
+from . import engine, grammar, ops, scoring, weights
 from .config import GromaConfig
 from .constants import DEFAULT_TOKENS, REGION_IDX_TOKENS, IGNORE_INDEX
 
@@ -57,6 +57,19 @@ class GenerateOutput(SimpleNamespace):
         for name in ("scores", "logprobs", "top_logprobs", "top_ids"):
             kw.setdefault(name, None)
         super().__init__(**kw)
+
+
+class ScoreOutput(SimpleNamespace):
+    """score(): teacher-forced log-probabilities of the caller's labels (semantics of forward(labels=...): the logits of expanded
+    position p score the label at p + 1; IGNORE_INDEX labels and the first label of a row are not scored).
+    token_logprobs / token_ranks / greedy_ids: lists of bs 1-D tensors (f32 / i32 / i64), one entry per scored label of the row in
+      position order -- natural-log probability under softmax of the raw logits, the number of ids ranked before the label (value
+      descending, id ascending; 0 = the label is the greedy token), and the greedy token of that position;
+    positions: list of bs i64 tensors, the index of each scored label in the caller's `labels` row;
+    num_tokens i64 [bs]; sequence_logprob f64 [bs]: the float64 sum of the row's fp32 values (0 for a row with nothing scored);
+    loss f64 scalar: -sum(logprob) / sum(num_tokens), HF's mean cross-entropy (NaN when nothing is scored);
+    pred_boxes: the selected boxes per image, as forward's vis_outputs; logits f32 [n_scored, vocab_size] of the scored rows in
+      (row, position) order with return_logits=True, else None."""
 
 
 def _c2c(b):  # HF center_to_corners_format
@@ -598,7 +611,7 @@ class GromaModel:
     def forward(self, input_ids=None, inputs_embeds=None, labels=None, attention_mask=None, images=None,
                 refer_boxes=None, ground_boxes=None, past_key_values=None, use_cache=False, output_attentions=False,
                 output_hidden_states=False, return_dict=False, _last_logits_only=False, _reserve=0, _cache=None,
-                _seeds=None, _keep_embeds=False):
+                _seeds=None, _keep_embeds=False, _score=None):
         if not self._loaded:
             raise RuntimeError("GromaModel has no weights: use from_pretrained / from_state_dict / from_synthetic")
         if output_attentions:
@@ -678,7 +691,11 @@ class GromaModel:
                 n_img_tok = (self.vit.G // 2) ** 2  # image tokens: groma.py:224-237, :361 (computed on the side stream)
                 # splice placeholders, embed, inject (groma.py:317-369)
                 new_ids_h, mask_h, flat, img_rows_h, reg_rows_h = self._host_splice_plan(ids_h, n_img_tok, n_reg)
-                if labels is not None:
+                if _score is not None:  # score(): where each of the caller's labels lands in the expanded sequence
+                    own = torch.arange(labels.shape[1], dtype=I64).expand(bs, -1)
+                    _score["plan"] = scoring.score_plan(self._splice_labels(ids_h, labels.cpu(), n_img_tok, n_reg),
+                                                        self._splice_labels(ids_h, own, n_img_tok, n_reg), self.config.vocab_size)
+                elif labels is not None:
                     labels = self._splice_labels(ids_h, labels.cpu(), n_img_tok, n_reg)
                 L = new_ids_h.shape[1]
                 assert img_rows_h.numel() == image_features.shape[0] and reg_rows_h.numel() == region_features.shape[0]
@@ -731,6 +748,15 @@ class GromaModel:
                 else:
                     emb = inputs_embeds.to(dev, F32).reshape(bs * L, -1).contiguous()
                 kv_len = None  # the reference rebuilds an all-ones mask over past+1 (groma.py:376-379, T6): every cached key is visible
+            if _score is not None:  # the head runs on the rows that carry a label, nowhere else: no [bs * L, V] logits
+                plan = _score["plan"]
+                res = None
+                if plan.rows.numel() > 0:  # (nothing scored: no LLaMA pass, no head launch)
+                    packed = torch.cat((plan.targets, plan.rows.to(I64))).to(dev, non_blocking=True)
+                    n = plan.rows.numel()
+                    res = self.llm.forward(emb, bs, L, cache, kv_len=kv_len,
+                                           head_rows=(packed[n:].to(I32), packed[:n], _score["head_rows"], _score["return_logits"]))
+                return self._score_output(plan, res, selected_boxes)
             states = [] if (output_hidden_states and self.all_hidden_states) else None
             logits, hn = self.llm.forward(emb, bs, L, cache, kv_len=kv_len, all_logits=not _last_logits_only, states=states)
 
@@ -760,6 +786,44 @@ class GromaModel:
                                       hidden_states=(hidden_states, vis_outputs), attentions=None)
 
     __call__ = forward
+
+    # ------------------------------------------------------------------ score
+    @_entry
+    def score(self, input_ids, labels, images=None, refer_boxes=None, ground_boxes=None, head_rows=2048, return_logits=False):
+        """Teacher-forced scoring: the log-probability of every label under the model, without decoding and without the
+        [bs * L, vocab] logits of forward(labels=...).  labels: int64, the shape of input_ids, IGNORE_INDEX where a token is not
+        scored; perception, placeholder splice, `<ground_box>` label rewrite (in place, as forward does) and HF's shift are
+        forward's.  head_rows: the head runs on at most that many labelled rows at a time (engine.LlamaEngine._head_rows).
+        Returns a ScoreOutput."""
+        if labels is None or input_ids is None or tuple(labels.shape) != tuple(input_ids.shape) or labels.dim() != 2:
+            raise ValueError("score needs input_ids and labels of one [bs, L] shape")
+        if labels.dtype != I64:
+            raise TypeError("labels must be int64")
+        if int(head_rows) < 1:
+            raise ValueError("head_rows must be at least 1")
+        lab_h = labels.detach().cpu()
+        bad = (lab_h != IGNORE_INDEX) & ((lab_h < 0) | (lab_h >= self.config.vocab_size))
+        bad[:, :1] = False  # (never scored)
+        if bool(bad.any()):  # before anything is launched
+            b, p = (int(x[0]) for x in bad.nonzero(as_tuple=True))
+            raise ValueError(f"label {int(lab_h[b, p])} (row {b}, position {p}) is outside the vocabulary [0, {self.config.vocab_size})")
+        return self.forward(input_ids=input_ids, labels=labels, images=images, refer_boxes=refer_boxes, ground_boxes=ground_boxes,
+                            _score=dict(head_rows=int(head_rows), return_logits=bool(return_logits)))
+
+    @staticmethod
+    def _score_output(plan, res, pred_boxes):
+        """ScoreOutput from the plan and what the rows-only head wrote (res None: nothing was scored)"""
+        n, counts = plan.rows.numel(), plan.counts.tolist()
+        if res is None:
+            lp, rank, greedy = torch.empty((0,), dtype=F32), torch.empty((0,), dtype=I32), torch.empty((0,), dtype=I64)
+        else:
+            lp, rank, greedy = res.logprob.cpu(), res.rank.cpu(), res.greedy.cpu()
+        seq = torch.stack([x.double().sum() for x in lp.split(counts)]) if counts else torch.empty((0,), dtype=torch.float64)
+        loss = -seq.sum() / n if n else torch.tensor(float("nan"), dtype=torch.float64)
+        return ScoreOutput(token_logprobs=list(lp.split(counts)), token_ranks=list(rank.split(counts)),
+                           greedy_ids=list(greedy.split(counts)), positions=list(plan.positions.split(counts)),
+                           num_tokens=plan.counts, sequence_logprob=seq, loss=loss, pred_boxes=pred_boxes,
+                           logits=res.logits if res is not None else None)
 
     def _splice_labels(self, ids_h, labels_h, n_img_tok, n_reg):
         new_labels = []

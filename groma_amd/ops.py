@@ -774,6 +774,49 @@ def sample_rows_lp(x, V, inv_temp, seed, pos=None, pos_stride=0, pos_off=0, out=
     return out, logprob
 
 
+def label_logprob_rows(x, V, labels, *, lse=None, greedy=None, rank=None, out=None):
+    """Teacher-forced scoring of logits rows (gr_label_logprob_rows, include/groma_hip.h): x f32 [rows, ld], labels int64 [rows] ->
+    logprob f32 [rows], the natural-log probability of labels[row] under softmax of x[row, :V] (0 where the label is negative:
+    IGNORE_INDEX rows are not read; NaN where it is >= V).  lse (f32), greedy (int64: first maximal index) and rank (int32: logits
+    ranked before the label, 0 = the label is the arg-max) are filled when given; True asks for a fresh tensor (out: logprob's).  Returns logprob
+    alone, or (logprob, lse, greedy, rank) -- None where not asked -- when any optional output was requested."""
+    lib = _lib.load()
+    _chk(x, F32, "x"); _chk(labels, I64, "labels")
+    rows = x.numel() // x.shape[-1]
+    if labels.numel() != rows:
+        raise ValueError("labels needs one entry per logits row")
+    asked = any(t is not None and t is not False for t in (lse, greedy, rank))
+    outs = []
+    for t, dt, name in ((lse, F32, "lse"), (greedy, I64, "greedy"), (rank, I32, "rank")):
+        if t is None or t is False:
+            t = None
+        elif t is True:
+            t = torch.empty((rows,), dtype=dt, device=x.device)
+        elif _chk(t, dt, name).numel() != rows:
+            raise ValueError(f"{name} needs one entry per logits row")
+        outs.append(t)
+    logprob = torch.empty((rows,), dtype=F32, device=x.device) if out is None else _chk(out, F32, "out")
+    if logprob.numel() != rows:
+        raise ValueError("out needs one entry per logits row")
+    _lib.check(lib.gr_label_logprob_rows(_p(x), rows, V, x.shape[-1], _p(labels), _p(logprob), _p(outs[0]), _p(outs[1]), _p(outs[2]),
+                                         _stream()), "gr_label_logprob_rows")
+    return (logprob, *outs) if asked else logprob
+
+
+def gather_rows(src, row_idx, out=None):
+    """out[r] = src[row_idx[r]]: fp32 rows by int32 index (gr_gather_rows_f32)"""
+    lib = _lib.load()
+    _chk(src, F32, "src"); _chk(row_idx, I32, "row_idx")
+    C = src.shape[-1]
+    if out is None:
+        out = torch.empty((row_idx.numel(), C), dtype=F32, device=src.device)
+    if _chk(out, F32, "out").numel() != row_idx.numel() * C:
+        raise ValueError("gather_rows: out does not match the index list")
+    _lib.check(lib.gr_gather_rows_f32(_p(src), _p(row_idx), _p(out), row_idx.numel(), C, src.numel() // C, _stream()),
+               "gr_gather_rows_f32")
+    return out
+
+
 def grammar_step(logits, V, state, n_boxes, ids, last_tok=None):
     """Grounded decoding (gr_grammar_step, include/groma_hip.h): advance every row's grammar state (int32 [rows], -1 = row not
     constrained) by its last token (int64 [rows]; None: no token yet) and write -inf over the ids the new state bans, in place, in

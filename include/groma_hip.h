@@ -328,6 +328,22 @@ int gr_sample_rows_lp(const float* x, long* out, float* logprob, int rows, int V
  * never NULL), R, bor, eor or a never id outside [0, V), bor == eor, bor or eor inside R. */
 int gr_grammar_step(float* logits, int rows, int V, long ld, int* state, const long* last_tok, const int* n_boxes,
                     long r_first, int r_count, long bor, long eor, const long* never, int n_never, hipStream_t stream);
+/* teacher-forced scoring (csrc/score.hip): per row of x f32 [rows, ld] (columns V..ld are never read), with t = labels[row]:
+ *   t < 0 (IGNORE_INDEX): the row's logits are not read; logprob = 0, lse = 0, greedy = -1, rank = -1.
+ *   t >= V: logprob = NaN, rank = -1; lse and greedy as below (nothing outside [0, V) is read).
+ *   else    lse     = m + log(sum_j exp(x[j] - m)), m = the row maximum;
+ *           logprob = x[t] - lse: the natural-log probability of the label under softmax of the raw logits;
+ *           greedy  = the first maximal index (gr_argmax_rows' tie rule);
+ *           rank    = #{j : x[j] > x[t], or x[j] == x[t] and j < t}  (0: the label is the greedy token).
+ * -inf logits are legal and carry no mass: a label at -inf gives logprob -inf; an all -inf row gives logprob NaN, lse -inf,
+ * greedy 0.  NaN logits are undefined.  lse, greedy and rank may be NULL.  One pass over each scored row (an online maximum /
+ * rescaled sum), one 256-thread workgroup per row, 16-byte loads (four scalar loads per vector where the row base is not 16-byte
+ * aligned: the same values in the same order), no global atomics; the summation order is fixed and written down in csrc/score.hip,
+ * so results are bit-reproducible.  EINVAL before any launch: NULL x / labels / logprob, rows <= 0, V <= 0, ld < V. */
+int gr_label_logprob_rows(const float* x, int rows, int V, long ld, const long* labels, float* logprob, float* lse, long* greedy,
+                          int* rank, hipStream_t stream);
+/* dst[r, :] = src[row_idx[r], :] for r < n: fp32 rows of C columns (C % 4 == 0); an index outside [0, src_rows) leaves a zero row */
+int gr_gather_rows_f32(const float* src, const int* row_idx, float* dst, long n, int C, long src_rows, hipStream_t stream);
 /* one step of HF 4.32 GenerationMixin.greedy_search bookkeeping on the device (reference: the loop HF runs around
  * groma/model/groma.py:176-200): n = unfinished ? nxt : pad; seq[:, *step] = n; tok = n; unfinished &= n != eos;
  * ++*step; pos[0..pos_rows) += inc_pos; *n_unfinished = sum(unfinished).  eos < 0 = no stopping token.
