@@ -73,59 +73,48 @@ extern "C" int gr_diag_att_clk(unsigned long long* out) { return (int)hipMemcpyF
 // 64-key V^T tile row is 128 physical elements (chunk 8*tt + g = hi of keys 32*tt + 8*g.., + 4 = lo), and both contractions
 // issue hi.hi + hi.lo + lo.hi.  P is split in registers.  Tiles are twice as large: one workgroup per CU.
 
-// De-phasing the two workgroups that share a CU (round 5).  A wave-iteration is ~1.0 k clk of MFMA followed by ~1.2 k clk of
-// soft-max VALU, and the two waves a SIMD holds (one from each resident workgroup) start together and then STAY in phase: while
-// both are in their MFMA segment they share the matrix pipe, while both are in the soft-max they share the VALU, so the pair
-// costs the SUM of the two segments (tests/diag/attn_clk.py) although the pipes are independent.  Two compile-time knobs break
-// the symmetry by the wave's hardware slot on its SIMD (HW_ID[3:0]; the two co-resident waves differ in it):
-//   ATT_PRIO_SLOT = p : odd slots run at s_setprio p -- the favoured wave gets through a contended segment first and the pair
-//                       settles half an iteration apart (MFMA of one under the soft-max of the other);
-//   ATT_SKEW = n      : the workgroup whose wave 0 sits in an odd slot sleeps n x 1024 clk before its first tile.
-#ifndef ATT_PRIO_SLOT
-#define ATT_PRIO_SLOT 0
-#endif
-#ifndef ATT_SKEW
-#define ATT_SKEW 0
-#endif
-// ATT_PRIO_PHASE = 1: s_setprio 1 around the two MFMA loops of an iteration (S^T = K.Q^T and O^T += V^T.P^T), 0 in the soft-max.
-// VALU issue between the waves of a SIMD is arbitrated by priority, then age (MI355X_MICROARCH.md "Two waves per SIMD", item 2): a
-// wave in its MFMA segment that loses issue slots to a co-resident wave's soft-max VALU also loses matrix-pipe time, while a
-// soft-max that yields to MFMA issues still gets the 3 of 4 issue slots an MFMA stream leaves free.
-#ifndef ATT_PRIO_PHASE
-#define ATT_PRIO_PHASE 0
-#endif
-#if ATT_PRIO_PHASE
-#define ATT_MFMA_BEGIN __builtin_amdgcn_s_setprio(1);
-#define ATT_MFMA_END __builtin_amdgcn_s_setprio(0);
-#else
-#define ATT_MFMA_BEGIN
-#define ATT_MFMA_END
-#endif
-
-// (score sub-tile j, k-step kk) of fragment e of prefetch group g.  Round 5: inside a group the k-step is the SLOW index when the
-// group spans several sub-tiles (hd 128: 8 fragments = 2 sub-tiles x 4 k-steps), so that consecutive MFMAs go to different
-// accumulators (s[u][j]: 2 q-tiles x 2 sub-tiles = 4 independent chains) instead of four dependent MFMAs per accumulator in a row.
-// Measured flat (profiles/r05_attn_variants.txt: 91.3 vs 91.6 us at 14 x 32 heads, 113.7 vs 112.2 us on the ViT shape, pair build 291.4
-// vs 291.6): the dependent-MFMA spacing is not what the kernel waits for.  OFF by default (= round 4's accumulation order, bitwise).
-#ifndef ATT_S_ORDER
-#define ATT_S_ORDER 0
-#endif
-template <int GK, int NKK>
-__device__ __forceinline__ constexpr int att_step_j(int g, int e) {
-  constexpr int NJ = GK / NKK;  // whole sub-tiles per group (0: a group is part of one sub-tile)
-  return (ATT_S_ORDER && NJ > 1) ? g * NJ + e % NJ : (g * GK + e) / NKK;
+// ---- the split-operand rule, in one place.  An MFMA operand fragment is one 16-B chunk, or a (hi, lo) pair of chunks.  Every helper
+// takes the two halves and touches `lo` in the pair build only.  Arrays of fragments carry the half as their LEADING dimension, of
+// size GR_SPW: [SP_HI] and [SP_LO], which name the one half in the 16-bit builds.  (Why lo first, q in two arrays and straight-line
+// `if constexpr` where a loop over the halves would do: each was tried the other way -- hi first, q's halves in one array, P's in two,
+// `for (h < GR_SPW)` around a load -- and each changed the register assignment or the schedule of a shipped code object
+// (tests/diag/isa_same.py).  They are free to change together with a measured change of the kernel.)
+constexpr int SP_LO = 0, SP_HI = GR_SPW - 1;
+union SpFrag { bf16x8 v; uint32_t w[4]; };
+// both halves from memory: at(0) is the address of the hi chunk, at(1) that of the lo chunk
+template <class F>
+__device__ __forceinline__ void sp_load(bf16x8& hi, bf16x8& lo, F&& at) {
+  hi = *(const bf16x8*)at(0);
+  if constexpr (GR_SP != 0) lo = *(const bf16x8*)at(1);
 }
-template <int GK, int NKK>
-__device__ __forceinline__ constexpr int att_step_kk(int g, int e) {
-  constexpr int NJ = GK / NKK;
-  return (ATT_S_ORDER && NJ > 1) ? e / NJ : (g * GK + e) % NKK;
+// the value a fragment holds in element e: the sum of its halves
+__device__ __forceinline__ float sp_get(const bf16x8& hi, const bf16x8& lo, int e) {
+  float x = bf2f((bf16_t)hi[e]);
+  if constexpr (GR_SP != 0) x += bf2f((bf16_t)lo[e]);
+  return x;
 }
-// ATT_SUM4: the soft-max row sum / row max of a lane's 16 scores as 4 independent partial chains (one per sub-tile) combined at the
-// end, instead of one serial chain of 16 dependent adds / 8 dependent max3 (dependent VALU issues at ~0.6 of the independent rate)
-// Measured neutral-to-slower (30.2 vs 29.0 us at 4 images, 115.0 vs 112.2 us on the ViT shape): OFF.
-#ifndef ATT_SUM4
-#define ATT_SUM4 0
-#endif
+// a pair of floats into word i of a fragment: split2, or split2_unit for values in [0, 1]
+template <bool UNIT>
+__device__ __forceinline__ void sp_put(SpFrag& hi, SpFrag& lo, int i, float a, float b) {
+  uint32_t l;
+  if constexpr (UNIT) split2_unit(a, b, hi.w[i], l);
+  else split2(a, b, hi.w[i], l);
+  if constexpr (GR_SP != 0) lo.w[i] = l;
+}
+// A contraction is one MFMA per accumulator, or three passes hi.hi, hi.lo, lo.hi: pass 2 takes the lo half of A, pass 1 that of B.
+// c(u) += a . b(u) for the QT query tiles that share the A fragment (b(u, lo) is a half of tile u's B fragment); each pass runs over
+// all tiles before the next one starts
+template <int QT, class FB, class FC>
+__device__ __forceinline__ void sp_contract(const bf16x8& a_hi, const bf16x8& a_lo, FB&& b, FC&& c) {
+#pragma unroll
+  for (int u = 0; u < QT; ++u) c(u) = GR_MFMA_16x16x32(a_hi, b(u, false), c(u));
+  if constexpr (GR_SP != 0) {
+#pragma unroll
+    for (int u = 0; u < QT; ++u) c(u) = GR_MFMA_16x16x32(a_hi, b(u, true), c(u));
+#pragma unroll
+    for (int u = 0; u < QT; ++u) c(u) = GR_MFMA_16x16x32(a_lo, b(u, false), c(u));
+  }
+}
 
 template <int I, int N, class F>
 __device__ __forceinline__ void att_static_for(F&& f) {
@@ -149,11 +138,6 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
   constexpr int VROW = KV * 2 * SPW;  // bytes per V^T tile row (128; split build 256)
   constexpr int VCH = VROW / 16;
   constexpr int VTILE = HD * VROW;    // Vt tile [HD][64] bf16
-#ifdef ATT_R04_PAIR  // A/B only (tests/diag): round 4's pair-build soft-max split and V^T swizzle
-  constexpr int VSWZ = 7;
-#else
-  constexpr int VSWZ = VCH - 1;       // V^T chunk swizzle mask: all chunk positions of a row (8, or 16 in the pair build)
-#endif
   constexpr int STAGE = KTILE + VTILE;
   // Key order inside a 64-key tile: MFMA row i of score sub-tile j holds key (j>>1)*32 + (i>>2)*8 + (j&1)*4 + (i&3),
   // so that after S^T = K.Q^T a lane (k-group fg) owns keys 32*tt + fg*8 + {0..7} of query fr: exactly the 8
@@ -165,12 +149,6 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fg = lane >> 4;
-#if ATT_PRIO_SLOT || ATT_SKEW
-  const unsigned hw_slot = __builtin_amdgcn_s_getreg((3 << 11) | 4);  // HW_REG_HW_ID bits [3:0]: wave slot on this SIMD
-#endif
-#if ATT_PRIO_SLOT
-  if (hw_slot & 1) __builtin_amdgcn_s_setprio(ATT_PRIO_SLOT);
-#endif
   // Block order: (batch, head) fastest, query block slowest and -- when causal -- the block with the most visible keys
   // first, so the long blocks start in the first wave of workgroups and the short ones fill the tail of the launch
   // (A/B on one box, tests/diag/attn_bench.py: L = 582 causal 14 x 32 heads 97.5 -> 96 us, 4 x 32 heads 34.1 -> 26.5 us;
@@ -230,7 +208,7 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
     for (int i = 0; i < NVC / 256; ++i) {
       const int q = i * 256 + tid;
       const int row = q / VCH, pos = q % VCH;
-      const int c = pos ^ (row & VSWZ);
+      const int c = pos ^ (row & (VCH - 1));
       const bf16_t* src;
       if constexpr (PAGED) src = p.vt + kv_vt_paged(pg, p.H, h, kv0, row, HD) + c * 8;
       else src = Vp + ((long)row * p.kv_stride + kv0) * SPW + c * 8;
@@ -242,21 +220,10 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
     stage_v(t);
   };
 
-  // ATT_STAGE_FIRST: tile 0's LDS-DMA is requested BEFORE the query fragments (and their RoPE tables) are fetched, so the two
-  // latencies of a workgroup's prologue overlap instead of adding up (a causal block at L = 582 runs only 2-10 tiles).
-#ifndef ATT_STAGE_FIRST
-#define ATT_STAGE_FIRST 0
-#endif
-#if ATT_STAGE_FIRST
-  if (ntiles > 0) stage(0);
-#endif
   // this lane's query rows (B-operand columns), one per q-tile -- clamp the tail
   int qi[QT], limit[QT];
   bool q_valid[QT];
-  bf16x8 qf[QT][HD / 32];
-#if GR_SP
-  bf16x8 qfl[QT][HD / 32];  // lo halves
-#endif
+  bf16x8 qf[QT][HD / 32], qfl[QT][HD / 32];  // hi, lo halves (two arrays: see the split-operand helpers)
 #pragma unroll
   for (int u = 0; u < QT; ++u) {
     qi[u] = q0 + wave * (16 * QT) + u * 16 + fr;
@@ -265,19 +232,14 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
 #pragma unroll
     for (int kk = 0; kk < HD / 32; ++kk) {
       const bf16_t* qsrc = p.q + sp_idx(q_base + (long)qi[u] * q_rs + kk * 32 + fg * 8);
-      qf[u][kk] = *(const bf16x8*)qsrc;
-#if GR_SP
-      qfl[u][kk] = *(const bf16x8*)(qsrc + 32);
-#endif
+      sp_load(qf[u][kk], qfl[u][kk], [&](int h) { return qsrc + 32 * h; });
     }
     if (p.rope_cos) {  // rotate in registers: out[d] = x[d]*cos - x[d+half]*sin (d < half), x[d]*cos + x[d-half]*sin (d >= half)
       constexpr int HALF = HD / 2, KH = HD / 64;  // fragments per half
       const float* cp = p.rope_cos + (long)(q_pos0 + qi[u]) * HALF + fg * 8;
       const float* sp = p.rope_sin + (long)(q_pos0 + qi[u]) * HALF + fg * 8;
-      bf16x8 rot[HD / 32];
-#if GR_SP
-      bf16x8 rotl[HD / 32];
-#endif
+      auto qval = [&](int kk, int e) { return sp_get(qf[u][kk], qfl[u][kk], e); };
+      bf16x8 rot[HD / 32], rotl[HD / 32];  // the rotated fragments, hi and lo
 #pragma unroll
       for (int kk = 0; kk < HD / 32; ++kk) {
         const int kp = kk < KH ? kk + KH : kk - KH;
@@ -285,31 +247,22 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
         const int dc = (kk % KH) * 32;
         const f32x4 c0 = *(const f32x4*)(cp + dc), c1 = *(const f32x4*)(cp + dc + 4);
         const f32x4 s0 = *(const f32x4*)(sp + dc), s1 = *(const f32x4*)(sp + dc + 4);
-        union { bf16x8 v; uint32_t w[4]; } o, ol;
+        SpFrag o, ol;
 #pragma unroll
         for (int e = 0; e < 8; e += 2) {
           const float ca = e < 4 ? c0[e] : c1[e - 4], cb = e < 4 ? c0[e + 1] : c1[e - 3];
           const float sa = e < 4 ? s0[e] : s1[e - 4], sb = e < 4 ? s0[e + 1] : s1[e - 3];
-#if GR_SP
-          const float x0 = bf2f((bf16_t)qf[u][kk][e]) + bf2f((bf16_t)qfl[u][kk][e]), x1 = bf2f((bf16_t)qf[u][kk][e + 1]) + bf2f((bf16_t)qfl[u][kk][e + 1]);
-          const float y0 = bf2f((bf16_t)qf[u][kp][e]) + bf2f((bf16_t)qfl[u][kp][e]), y1 = bf2f((bf16_t)qf[u][kp][e + 1]) + bf2f((bf16_t)qfl[u][kp][e + 1]);
-#else
-          const float x0 = bf2f((bf16_t)qf[u][kk][e]), x1 = bf2f((bf16_t)qf[u][kk][e + 1]);
-          const float y0 = bf2f((bf16_t)qf[u][kp][e]), y1 = bf2f((bf16_t)qf[u][kp][e + 1]);
-#endif
-          split2(x0 * ca + sgn * y0 * sa, x1 * cb + sgn * y1 * sb, o.w[e >> 1], ol.w[e >> 1]);
+          const float x0 = qval(kk, e), x1 = qval(kk, e + 1);
+          const float y0 = qval(kp, e), y1 = qval(kp, e + 1);
+          sp_put<false>(o, ol, e >> 1, x0 * ca + sgn * y0 * sa, x1 * cb + sgn * y1 * sb);
         }
         rot[kk] = o.v;
-#if GR_SP
-        rotl[kk] = ol.v;
-#endif
+        if (GR_SP) rotl[kk] = ol.v;
       }
 #pragma unroll
       for (int kk = 0; kk < HD / 32; ++kk) {
         qf[u][kk] = rot[kk];
-#if GR_SP
-        qfl[u][kk] = rotl[kk];
-#endif
+        if (GR_SP) qfl[u][kk] = rotl[kk];
       }
     }
     limit[u] = p.causal ? min(kvmax, q_pos0 + qi[u] + 1) : kvmax;  // keys [0, limit) visible
@@ -327,18 +280,7 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
 #ifdef G256_CLK
   unsigned long long am[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-#if !ATT_STAGE_FIRST
   if (ntiles > 0) stage(0);
-#endif
-#if ATT_SKEW
-  {
-    __shared__ int skew;
-    if (tid == 0) skew = (int)(hw_slot & 1);
-    __syncthreads();
-    if (skew)
-      for (int i = 0; i < ATT_SKEW; ++i) __builtin_amdgcn_s_sleep(16);
-  }
-#endif
   // ---- the three pieces of an iteration (shared by the plain loop and the pipelined one, ATT_PIPE)
   // S^T tiles: rows = keys (4 sub-tiles of 16), col = this lane's query (per q-tile); K fragments shared.
   // K fragments are read one group AHEAD of the MFMAs that use them (double buffer, GK fragments per group): the
@@ -346,15 +288,12 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
   constexpr int GK = ATT_G;                   // fragments per group
   constexpr int NKK = HD / 32;                // k-steps per score sub-tile
   constexpr int NKG = 4 * NKK / GK;           // groups over (j, kk)
-  auto load_k = [&](const char* ksm, int g, bf16x8* dst) {
+  auto load_k = [&](const char* ksm, int g, bf16x8 (*dst)[GK]) {
 #pragma unroll
     for (int e = 0; e < GK; ++e) {
-      const int j = att_step_j<GK, NKK>(g, e), kk = att_step_kk<GK, NKK>(g, e);
+      const int j = (g * GK + e) / NKK, kk = (g * GK + e) % NKK;
       const int row = (j >> 1) * 32 + (fr >> 2) * 8 + (j & 1) * 4 + (fr & 3);
-      dst[e] = *(const bf16x8*)(ksm + row * KROW + (((kk * 4 * SPW + fg) ^ kswz(row)) << 4));
-#if GR_SP
-      dst[GK + e] = *(const bf16x8*)(ksm + row * KROW + (((kk * 8 + 4 + fg) ^ kswz(row)) << 4));
-#endif
+      sp_load(dst[SP_HI][e], dst[SP_LO][e], [&](int h) { return ksm + row * KROW + (((kk * 4 * SPW + 4 * h + fg) ^ kswz(row)) << 4); });
     }
   };
   auto compute_S = [&](const char* ksm, f32x4 (&s)[QT][4]) {
@@ -362,77 +301,39 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
     for (int u = 0; u < QT; ++u)
 #pragma unroll
       for (int j = 0; j < 4; ++j) s[u][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    bf16x8 kfr[2][GK * SPW];  // split build: [.., GK + e] = lo halves
+    bf16x8 kfr[2][SPW][GK];  // [buffer][half][fragment]
     load_k(ksm, 0, kfr[0]);
-    ATT_MFMA_BEGIN
 #pragma unroll
     for (int g = 0; g < NKG; ++g) {
       if (g + 1 < NKG) load_k(ksm, g + 1, kfr[(g + 1) & 1]);
       __builtin_amdgcn_sched_barrier(0);
-#if GR_SP && ATT_S_ORDER
-      // pair build: the three passes are the SLOW index, so an accumulator is revisited every GK * QT MFMAs, not every QT
-#pragma unroll
-      for (int pp = 0; pp < 3; ++pp)
-#pragma unroll
-        for (int e = 0; e < GK; ++e) {
-          const int j = att_step_j<GK, NKK>(g, e), kk = att_step_kk<GK, NKK>(g, e);
-#pragma unroll
-          for (int u = 0; u < QT; ++u)
-            s[u][j] = GR_MFMA_16x16x32(kfr[g & 1][pp == 2 ? GK + e : e], pp == 1 ? qfl[u][kk] : qf[u][kk], s[u][j]);
-        }
-#else
 #pragma unroll
       for (int e = 0; e < GK; ++e) {
-        const int j = att_step_j<GK, NKK>(g, e), kk = att_step_kk<GK, NKK>(g, e);
-#pragma unroll
-        for (int u = 0; u < QT; ++u) s[u][j] = GR_MFMA_16x16x32(kfr[g & 1][e], qf[u][kk], s[u][j]);
-#if GR_SP
-#pragma unroll
-        for (int u = 0; u < QT; ++u) s[u][j] = GR_MFMA_16x16x32(kfr[g & 1][e], qfl[u][kk], s[u][j]);
-#pragma unroll
-        for (int u = 0; u < QT; ++u) s[u][j] = GR_MFMA_16x16x32(kfr[g & 1][GK + e], qf[u][kk], s[u][j]);
-#endif
+        const int j = (g * GK + e) / NKK, kk = (g * GK + e) % NKK;
+        sp_contract<QT>(kfr[g & 1][SP_HI][e], kfr[g & 1][SP_LO][e], [&](int u, bool lo) { return lo ? qfl[u][kk] : qf[u][kk]; },
+                        [&](int u) -> f32x4& { return s[u][j]; });
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
-    ATT_MFMA_END
   };
   // online softmax; lane holds keys kv0 + (j>>1)*32 + fg*8 + (j&1)*4 + r of query fr (per q-tile).
   // The running max is kept in RAW score units and the softmax scale is folded into one fma per element
   // (e = exp2(s*c - m*c)); masking (2 cmp + 2 select per element) is compiled only into boundary tiles.
-  union PB { bf16x8 v; uint32_t w[4]; };
-  PB pb[QT][2];
-#if GR_SP
-  PB pbl[QT][2];  // lo halves of P
-#endif
+  SpFrag pb[SPW][QT][2];  // [half][q-tile][key half]
   const float cs = p.scale_log2;
-#if GR_SP
-#ifdef ATT_R04_PAIR
-#define ATT_SPLIT_P split2
-#else
-#define ATT_SPLIT_P split2_unit   // (P in [0, 1]: no saturation)
-#endif
-#endif
   // P^T of q-tile u, key half tt, as the B operand; k-slot (fg,e) <-> key 32*tt + fg*8 + e (standard contiguous slot)
   auto pack_p = [&](f32x4 (&s)[QT][4], int u, int tt) {
-#if GR_SP
-    ATT_SPLIT_P(s[u][2 * tt][0], s[u][2 * tt][1], pb[u][tt].w[0], pbl[u][tt].w[0]);
-    ATT_SPLIT_P(s[u][2 * tt][2], s[u][2 * tt][3], pb[u][tt].w[1], pbl[u][tt].w[1]);
-    ATT_SPLIT_P(s[u][2 * tt + 1][0], s[u][2 * tt + 1][1], pb[u][tt].w[2], pbl[u][tt].w[2]);
-    ATT_SPLIT_P(s[u][2 * tt + 1][2], s[u][2 * tt + 1][3], pb[u][tt].w[3], pbl[u][tt].w[3]);
-#else
-    pb[u][tt].w[0] = pack2bf_unit(s[u][2 * tt][0], s[u][2 * tt][1]);
-    pb[u][tt].w[1] = pack2bf_unit(s[u][2 * tt][2], s[u][2 * tt][3]);
-    pb[u][tt].w[2] = pack2bf_unit(s[u][2 * tt + 1][0], s[u][2 * tt + 1][1]);
-    pb[u][tt].w[3] = pack2bf_unit(s[u][2 * tt + 1][2], s[u][2 * tt + 1][3]);
-#endif
+    SpFrag &hi = pb[SP_HI][u][tt], &lo = pb[SP_LO][u][tt];  // (P in [0, 1]: no saturation)
+    sp_put<true>(hi, lo, 0, s[u][2 * tt][0], s[u][2 * tt][1]);
+    sp_put<true>(hi, lo, 1, s[u][2 * tt][2], s[u][2 * tt][3]);
+    sp_put<true>(hi, lo, 2, s[u][2 * tt + 1][0], s[u][2 * tt + 1][1]);
+    sp_put<true>(hi, lo, 3, s[u][2 * tt + 1][2], s[u][2 * tt + 1][3]);
   };
   auto softmax_tile = [&](auto masked_tag, f32x4 (&s)[QT][4], int kv0) {
     constexpr bool MASKED = decltype(masked_tag)::value;
 #pragma unroll
     for (int u = 0; u < QT; ++u) {
-      float mxp[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
+      float mx = -1e30f;
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -441,14 +342,15 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
             const int key = kv0 + (j >> 1) * 32 + fg * 8 + (j & 1) * 4 + r;
             if (key >= limit[u]) s[u][j][r] = -1e30f;
           }
-          mxp[ATT_SUM4 ? j : 0] = fmaxf(mxp[ATT_SUM4 ? j : 0], s[u][j][r]);
+          mx = fmaxf(mx, s[u][j][r]);
         }
-      float mx = fmaxf(fmaxf(mxp[0], mxp[1]), fmaxf(mxp[2], mxp[3]));
-      mx = rows_max(mx);
+      // (the extra max with -1e30 here and the + 0.f below are value-neutral: kept so that the code object is unchanged; removing
+      // them is a separate, measured change)
+      mx = rows_max(fmaxf(fmaxf(mx, -1e30f), -1e30f));
       const float m_new = fmaxf(m_run[u], mx);
       const float alpha = __builtin_amdgcn_exp2f((m_run[u] - m_new) * cs);
       const float mc = -m_new * cs;
-      float rsp[4] = {0.f, 0.f, 0.f, 0.f};
+      float rs = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -458,10 +360,9 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
           float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[u][j][r], cs, mc));
           if (MASKED) e = s[u][j][r] <= -1e30f ? 0.f : e;
           s[u][j][r] = e;
-          rsp[ATT_SUM4 ? j : 0] += e;
+          rs += e;
         }
-      float rs = (rsp[0] + rsp[1]) + (rsp[2] + rsp[3]);
-      rs = rows_sum(rs);
+      rs = rows_sum((rs + 0.f) + 0.f);
       l_run[u] = l_run[u] * alpha + rs;
       m_run[u] = m_new;
 #pragma unroll
@@ -474,8 +375,8 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
   auto compute_PV = [&](const char* vsm) {
     constexpr int GV = ATT_G;
     constexpr int NG = 2 * (HD / 16) / GV;  // groups of GV (tt, n) steps
-    bf16x8 vfr[2][GV * SPW];
-    auto load_v = [&](int g, bf16x8* dst) {
+    bf16x8 vfr[2][SPW][GV];
+    auto load_v = [&](int g, bf16x8 (*dst)[GV]) {
 #pragma unroll
       for (int e = 0; e < GV; ++e) {
         const int step = g * GV + e, tt = step / (HD / 16), n = step % (HD / 16);
@@ -483,45 +384,22 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
         const int c = tt * 4 * SPW + fg;  // keys 32*tt + fg*8 .. +7 = one 16-B chunk of the Vt row
         // chunk swizzle over ALL chunk positions of a V^T row: 8 in the 16-bit builds, 16 in the pair build (256-B rows start on
         // bank 0 there, and `row & 7` left the 16 rows a ds_read_b128 lane group touches 2-way conflicted -- round 5)
-        dst[e] = *(const bf16x8*)(vsm + row * VROW + ((c ^ (row & VSWZ)) << 4));
-#if GR_SP
-        dst[GV + e] = *(const bf16x8*)(vsm + row * VROW + (((c + 4) ^ (row & VSWZ)) << 4));
-#endif
+        sp_load(dst[SP_HI][e], dst[SP_LO][e], [&](int h) { return vsm + row * VROW + (((c + 4 * h) ^ (row & (VCH - 1))) << 4); });
       }
     };
     load_v(0, vfr[0]);
-    ATT_MFMA_BEGIN
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
       if (g + 1 < NG) load_v(g + 1, vfr[(g + 1) & 1]);
       __builtin_amdgcn_sched_barrier(0);
-#if GR_SP && ATT_S_ORDER
-#pragma unroll
-      for (int pp = 0; pp < 3; ++pp)   // (passes slow, fragments fast: an accumulator is revisited every GV * QT MFMAs)
-#pragma unroll
-        for (int e = 0; e < GV; ++e) {
-          const int step = g * GV + e, tt = step / (HD / 16), n = step % (HD / 16);
-#pragma unroll
-          for (int u = 0; u < QT; ++u)
-            o[u][n] = GR_MFMA_16x16x32(vfr[g & 1][pp == 2 ? GV + e : e], pp == 1 ? pbl[u][tt].v : pb[u][tt].v, o[u][n]);
-        }
-#else
 #pragma unroll
       for (int e = 0; e < GV; ++e) {
         const int step = g * GV + e, tt = step / (HD / 16), n = step % (HD / 16);
-#pragma unroll
-        for (int u = 0; u < QT; ++u) o[u][n] = GR_MFMA_16x16x32(vfr[g & 1][e], pb[u][tt].v, o[u][n]);
-#if GR_SP
-#pragma unroll
-        for (int u = 0; u < QT; ++u) o[u][n] = GR_MFMA_16x16x32(vfr[g & 1][e], pbl[u][tt].v, o[u][n]);
-#pragma unroll
-        for (int u = 0; u < QT; ++u) o[u][n] = GR_MFMA_16x16x32(vfr[g & 1][GV + e], pb[u][tt].v, o[u][n]);
-#endif
+        sp_contract<QT>(vfr[g & 1][SP_HI][e], vfr[g & 1][SP_LO][e], [&](int u, bool lo) { return pb[lo ? SP_LO : SP_HI][u][tt].v; },
+                        [&](int u) -> f32x4& { return o[u][n]; });
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
-    ATT_MFMA_END
   };
 
 #if ATT_PIPE
@@ -531,10 +409,9 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
   // then P.V of tile t.  K is staged one tile ahead of V^T in the same two LDS stages.  Same operations in the same order per
   // accumulator as the plain loop: bitwise-identical results (tests/diag/attn_variants.py).  Boundary tiles (masked soft-max) and
   // the last tile run the plain pieces.
-  static_assert(!ATT_S_ORDER && !ATT_SUM4, "the pipelined loop implements the default accumulation order");
   const int nt_w = wave_has_rows ? min(ntiles, (wav_limit + KV - 1) / KV) : 0;  // this wave computes tiles [0, nt_w)
   auto fused = [&](const char* ksm, f32x4 (&cur)[QT][4], f32x4 (&nxt)[QT][4]) {
-    constexpr int PASSES = GR_SP ? 3 : 1;
+    constexpr int PASSES = GR_SP ? 3 : 1;      // (sp_contract's passes, one MFMA per step here)
     constexpr int NM = 4 * NKK * PASSES * QT;  // score MFMAs of a tile
     constexpr int NO = HD / 16;
     // soft-max steps per q-tile: 4 max, 1 row max, 18 of the exp phase (software-pipelined over the 16 scores: the fma of score k, the
@@ -542,7 +419,7 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
     constexpr int NVU = 26 + NO;
     constexpr int NV = QT * NVU;
     constexpr int PRE = ATT_PIPE_PRE;          // soft-max steps ahead of the first MFMA (in the shadow of the first K fragment reads)
-    bf16x8 kfr[2][GK * SPW];
+    bf16x8 kfr[2][SPW][GK];
     float mx[QT], m_new[QT], alpha[QT], mc[QT], rs[QT];
     auto valu = [&](auto kc) {
       constexpr int k = decltype(kc)::value;
@@ -585,11 +462,7 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
       constexpr int g = ge / GK, e = ge % GK, j = ge / NKK, kk = ge % NKK;
       if constexpr (e == 0 && pass == 0 && u == 0 && g + 1 < NKG) load_k(ksm, g + 1, kfr[(g + 1) & 1]);
       const f32x4 c = (kk == 0 && pass == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : nxt[u][j];
-#if GR_SP
-      nxt[u][j] = GR_MFMA_16x16x32(kfr[g & 1][pass == 2 ? GK + e : e], pass == 1 ? qfl[u][kk] : qf[u][kk], c);
-#else
-      nxt[u][j] = GR_MFMA_16x16x32(kfr[g & 1][e], qf[u][kk], c);
-#endif
+      nxt[u][j] = GR_MFMA_16x16x32(kfr[g & 1][pass == 2 ? SP_LO : SP_HI][e], pass == 1 ? qfl[u][kk] : qf[u][kk], c);
     };
     load_k(ksm, 0, kfr[0]);
     __builtin_amdgcn_sched_barrier(0);
@@ -672,14 +545,10 @@ __global__ __launch_bounds__(256, GR_SP ? 1 : 2) void attention_kernel(AttnArgs 
   }
 }
 
-extern "C" int gr_attention_bf16(const void* q, const void* k, const void* vt, void* out, const int* kv_len, int B, int H,
-                                 int Lq, int Skv, int kv_stride, int head_dim, int causal, int q_pos0, float scale,
-                                 const int* pos_dev, int pos_stride, long q_ld, const float* rope_cos,
-                                 const float* rope_sin, hipStream_t stream) {
-  if (!q || !k || !vt || !out || B <= 0 || H <= 0 || Lq <= 0 || Skv <= 0) return GR_EINVAL;
-  if (kv_stride % 64 != 0 || kv_stride < Skv) return GR_EINVAL;  // Vt tile reads run to the next multiple of 64
-  if (GR_SP && q_ld % 32 != 0) return GR_EINVAL;
-  AttnArgs p;
+// What gr_attention_bf16 and gr_attention_paged share: the checks on q_ld / rope_*, the argument block, and the launch
+static int attn_fill(AttnArgs& p, const void* q, const void* k, const void* vt, void* out, const int* kv_len, int B, int H, int Lq,
+                     int Skv, int kv_stride, int head_dim, int causal, int q_pos0, float scale, const int* pos_dev, int pos_stride,
+                     long q_ld, const float* rope_cos, const float* rope_sin, const int* table, int table_ld) {
   p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vt = (const bf16_t*)vt; p.out = (bf16_t*)out;
   p.kv_len = kv_len;
   p.pos_dev = pos_dev; p.pos_stride = pos_stride;
@@ -689,16 +558,34 @@ extern "C" int gr_attention_bf16(const void* q, const void* k, const void* vt, v
   p.B = B; p.H = H; p.Lq = Lq; p.Skv = Skv; p.kv_stride = kv_stride;
   p.causal = causal; p.q_pos0 = q_pos0;
   p.scale_log2 = scale * 1.44269504088896340736f;
-  p.table = nullptr; p.table_ld = 0;
-  dim3 grid(B * H, gr_cdiv(Lq, 128));
-  if (gr_set_max_lds((const void*)attention_kernel<128>, 65536 * GR_SPW) != hipSuccess ||
-      gr_set_max_lds((const void*)attention_kernel<64>, 32768 * GR_SPW) != hipSuccess)
+  p.table = table; p.table_ld = table_ld;
+  return GR_OK;
+}
+template <bool PAGED>
+static int attn_launch(const AttnArgs& p, int head_dim, hipStream_t stream) {
+  dim3 grid(p.B * p.H, gr_cdiv(p.Lq, 128));
+  if (gr_set_max_lds((const void*)attention_kernel<128, PAGED>, 65536 * GR_SPW) != hipSuccess ||
+      gr_set_max_lds((const void*)attention_kernel<64, PAGED>, 32768 * GR_SPW) != hipSuccess)
     return GR_EINVAL;
-  if (head_dim == 128) hipLaunchKernelGGL(attention_kernel<128>, grid, dim3(256), 65536 * GR_SPW, stream, p);
-  else if (head_dim == 64) hipLaunchKernelGGL(attention_kernel<64>, grid, dim3(256), 32768 * GR_SPW, stream, p);
+  if (head_dim == 128) hipLaunchKernelGGL((attention_kernel<128, PAGED>), grid, dim3(256), 65536 * GR_SPW, stream, p);
+  else if (head_dim == 64) hipLaunchKernelGGL((attention_kernel<64, PAGED>), grid, dim3(256), 32768 * GR_SPW, stream, p);
   else return GR_EINVAL;
   GR_CHECK_LAUNCH();
   return GR_OK;
+}
+
+extern "C" int gr_attention_bf16(const void* q, const void* k, const void* vt, void* out, const int* kv_len, int B, int H,
+                                 int Lq, int Skv, int kv_stride, int head_dim, int causal, int q_pos0, float scale,
+                                 const int* pos_dev, int pos_stride, long q_ld, const float* rope_cos,
+                                 const float* rope_sin, hipStream_t stream) {
+  if (!q || !k || !vt || !out || B <= 0 || H <= 0 || Lq <= 0 || Skv <= 0) return GR_EINVAL;
+  if (kv_stride % 64 != 0 || kv_stride < Skv) return GR_EINVAL;  // Vt tile reads run to the next multiple of 64
+  if (GR_SP && q_ld % 32 != 0) return GR_EINVAL;
+  AttnArgs p;
+  if (attn_fill(p, q, k, vt, out, kv_len, B, H, Lq, Skv, kv_stride, head_dim, causal, q_pos0, scale, pos_dev, pos_stride, q_ld,
+                rope_cos, rope_sin, nullptr, 0) != GR_OK)
+    return GR_EINVAL;
+  return attn_launch<false>(p, head_dim, stream);
 }
 
 // Paged form (kv_layout.h): causal attention of Lq new positions per row over a paged cache -- the suffix prefill of the continuous
@@ -713,25 +600,10 @@ extern "C" int gr_attention_paged(const void* q, const void* k_pool, const void*
   if (!q || !k_pool || !vt_pool || !out || !block_table || B <= 0 || H <= 0 || Lq <= 0) return GR_EINVAL;
   if (table_ld <= 0 || table_ld * KV_PAGE > 8192 || (head_dim != 128 && head_dim != 64)) return GR_EINVAL;
   if (!pos_dev && (q_pos0 < 0 || q_pos0 + Lq > table_ld * KV_PAGE)) return GR_EINVAL;
-  if (q_ld < 0 || (q_ld > 0 && (q_ld % 8 != 0 || q_ld < (long)H * head_dim)) || (rope_cos == nullptr) != (rope_sin == nullptr))
-    return GR_EINVAL;
-#if !GR_SP
   AttnArgs p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k_pool; p.vt = (const bf16_t*)vt_pool; p.out = (bf16_t*)out;
-  p.kv_len = kv_len;
-  p.pos_dev = pos_dev; p.pos_stride = pos_stride;
-  p.q_ld = q_ld; p.rope_cos = rope_cos; p.rope_sin = rope_sin;
-  p.B = B; p.H = H; p.Lq = Lq; p.Skv = q_pos0 + Lq; p.kv_stride = KV_PAGE;
-  p.causal = 1; p.q_pos0 = q_pos0;
-  p.scale_log2 = scale * 1.44269504088896340736f;
-  p.table = block_table; p.table_ld = table_ld;
-  dim3 grid(B * H, gr_cdiv(Lq, 128));
-  if (gr_set_max_lds((const void*)attention_kernel<128, true>, 65536) != hipSuccess ||
-      gr_set_max_lds((const void*)attention_kernel<64, true>, 32768) != hipSuccess)
+  if (attn_fill(p, q, k_pool, vt_pool, out, kv_len, B, H, Lq, q_pos0 + Lq, KV_PAGE, head_dim, 1, q_pos0, scale, pos_dev, pos_stride,
+                q_ld, rope_cos, rope_sin, block_table, table_ld) != GR_OK)
     return GR_EINVAL;
-  if (head_dim == 128) hipLaunchKernelGGL((attention_kernel<128, true>), grid, dim3(256), 65536, stream, p);
-  else hipLaunchKernelGGL((attention_kernel<64, true>), grid, dim3(256), 32768, stream, p);
-  GR_CHECK_LAUNCH();
-#endif
+  if constexpr (GR_SP == 0) return attn_launch<true>(p, head_dim, stream);  // (the paged kernels do not exist in the pair build)
   return GR_OK;
 }

@@ -166,6 +166,28 @@ __global__ __launch_bounds__(1024) void decode_attention_kernel(const bf16_t* __
   if (tid == 0 && blockIdx.z == 0) { wo[HD] = mx; wo[HD + 1] = denom; }
 }
 
+#ifndef DA_DSPLIT_MAX_BLOCKS
+#define DA_DSPLIT_MAX_BLOCKS 128
+#endif
+// The (head_dim, output-dim split) dispatch of both entry points.  The slot form passes (kv_stride, nullptr, 0, 0) for the cache
+// geometry, the paged form (Smax, block_table, table_ld, sc_len): there kv_stride carries the row capacity, and the visible length
+// of a row never reaches past its table.
+template <bool PAGED>
+static int decode_attention_launch(int head_dim, size_t lds, hipStream_t stream, const void* q, const void* k, const void* vt, void* out,
+                                   const int* kv_len, int B, int H, int kv_stride, int q_pos0, float scale, const int* pos_dev,
+                                   int pos_stride, int nsplit, float* parts, const int* table, int table_ld, int sc_len) {
+  const int ds = B * H * nsplit <= DA_DSPLIT_MAX_BLOCKS ? 2 : 1;  // fewer blocks than half the CUs: two per (row, head) along the output dims
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(B * H, nsplit, ds), dim3(1024), lds, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt,
+                       (bf16_t*)out, kv_len, H, kv_stride, q_pos0, scale, pos_dev, pos_stride, parts, table, table_ld, sc_len);
+  };
+  if (head_dim == 128) { if (ds == 2) launch(decode_attention_kernel<128, 2, PAGED>); else launch(decode_attention_kernel<128, 1, PAGED>); }
+  else if (head_dim == 64) { if (ds == 2) launch(decode_attention_kernel<64, 2, PAGED>); else launch(decode_attention_kernel<64, 1, PAGED>); }
+  else return GR_EINVAL;
+  GR_CHECK_LAUNCH();
+  return GR_OK;
+}
+
 extern "C" int gr_decode_attention(const void* q, const void* k, const void* vt, void* out, const int* kv_len, int B, int H,
                                    int Smax, int kv_stride, int head_dim, int q_pos0, float scale, const int* pos_dev,
                                    int pos_stride, int nsplit, float* parts, hipStream_t stream) {
@@ -174,20 +196,8 @@ extern "C" int gr_decode_attention(const void* q, const void* k, const void* vt,
   if (nsplit < 1 || nsplit > 16 || (nsplit > 1 && !parts)) return GR_EINVAL;
   if (kv_stride % 64 != 0 || kv_stride < Smax || (!pos_dev && q_pos0 + 1 > Smax)) return GR_EINVAL;
   const size_t lds = (size_t)((Smax + 63) & ~63) * sizeof(float);
-#ifndef DA_DSPLIT_MAX_BLOCKS
-#define DA_DSPLIT_MAX_BLOCKS 128
-#endif
-  const int ds = B * H * nsplit <= DA_DSPLIT_MAX_BLOCKS ? 2 : 1;  // fewer blocks than half the CUs: two per (row, head) along the output dims
-#define LAUNCH_DA(HDV, DSV)                                                                                                    \
-  hipLaunchKernelGGL((decode_attention_kernel<HDV, DSV>), dim3(B * H, nsplit, DSV), dim3(1024), lds, stream, (const bf16_t*)q, \
-                     (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)out, kv_len, H, kv_stride, q_pos0, scale, pos_dev,         \
-                     pos_stride, parts, nullptr, 0, 0)
-  if (head_dim == 128) { if (ds == 2) LAUNCH_DA(128, 2); else LAUNCH_DA(128, 1); }
-  else if (head_dim == 64) { if (ds == 2) LAUNCH_DA(64, 2); else LAUNCH_DA(64, 1); }
-  else return GR_EINVAL;
-#undef LAUNCH_DA
-  GR_CHECK_LAUNCH();
-  return GR_OK;
+  return decode_attention_launch<false>(head_dim, lds, stream, q, k, vt, out, kv_len, B, H, kv_stride, q_pos0, scale, pos_dev, pos_stride,
+                                        nsplit, parts, nullptr, 0, 0);
 }
 
 // Paged form (kv_layout.h): k_pool and vt_pool are the page pools, block_table row b is batch row b's table.
@@ -201,16 +211,6 @@ extern "C" int gr_decode_attention_paged(const void* q, const void* k_pool, cons
   if (!pos_dev && (q_pos0 < 0 || q_pos0 + 1 > Smax)) return GR_EINVAL;
   const int sc_len = (Smax + 63) & ~63;
   const size_t lds = (size_t)sc_len * sizeof(float) + (size_t)(sc_len / KV_PAGE) * sizeof(int);
-  const int ds = B * H * nsplit <= DA_DSPLIT_MAX_BLOCKS ? 2 : 1;
-  // kv_stride carries the row capacity (Smax): the visible length of a row never reaches past its table
-#define LAUNCH_DAP(HDV, DSV)                                                                                                     \
-  hipLaunchKernelGGL((decode_attention_kernel<HDV, DSV, true>), dim3(B * H, nsplit, DSV), dim3(1024), lds, stream,               \
-                     (const bf16_t*)q, (const bf16_t*)k_pool, (const bf16_t*)vt_pool, (bf16_t*)out, kv_len, H, Smax, q_pos0, scale, \
-                     pos_dev, pos_stride, parts, block_table, table_ld, sc_len)
-  if (head_dim == 128) { if (ds == 2) LAUNCH_DAP(128, 2); else LAUNCH_DAP(128, 1); }
-  else if (head_dim == 64) { if (ds == 2) LAUNCH_DAP(64, 2); else LAUNCH_DAP(64, 1); }
-  else return GR_EINVAL;
-#undef LAUNCH_DAP
-  GR_CHECK_LAUNCH();
-  return GR_OK;
+  return decode_attention_launch<true>(head_dim, lds, stream, q, k_pool, vt_pool, out, kv_len, B, H, Smax, q_pos0, scale, pos_dev,
+                                       pos_stride, nsplit, parts, block_table, table_ld, sc_len);
 }

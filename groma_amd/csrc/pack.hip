@@ -174,28 +174,36 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const bf16_t* __restrict
 
 #endif  // GR_SP
 
+// The head_dim dispatch of gr_qkv_split, gr_qkv_split_paged and gr_kv_append_paged (the pair build has the slot form only, and its
+// kernel takes no block table)
+template <bool PAGED, bool APPEND>
+static int qkv_split_launch(dim3 grid, hipStream_t stream, int head_dim, const void* qkv, void* q, void* k, void* vt, const float* cosT,
+                            const float* sinT, int B, int H, int L, int pos0, int kv_stride, const int* pos_dev, int pos_stride,
+                            const int* table, int table_ld) {
+  auto launch = [&](auto kernel, auto... tail) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k, (bf16_t*)vt, cosT, sinT, B, H, L,
+                       pos0, kv_stride, pos_dev, pos_stride, tail...);
+  };
+#if GR_SP
+  if (head_dim == 128) launch(qkv_split_kernel<128>);
+  else if (head_dim == 64) launch(qkv_split_kernel<64>);
+#else
+  if (head_dim == 128) launch(qkv_split_kernel<128, PAGED, APPEND>, table, table_ld);
+  else if (head_dim == 64) launch(qkv_split_kernel<64, PAGED, APPEND>, table, table_ld);
+#endif
+  else return GR_EINVAL;
+  GR_CHECK_LAUNCH();
+  return GR_OK;
+}
+
 extern "C" int gr_qkv_split(const void* qkv, void* q, void* k, void* vt, const float* cosT, const float* sinT, int B,
                             int H, int L, int head_dim, int pos0, int kv_stride, const int* pos_dev, int pos_stride,
                             hipStream_t stream) {
   if (!qkv || !k || !vt || B <= 0 || H <= 0 || L <= 0) return GR_EINVAL;  // q may be NULL (left in qkv)
   if ((cosT == nullptr) != (sinT == nullptr)) return GR_EINVAL;
   if (GR_SP && kv_stride % 32 != 0) return GR_EINVAL;
-  dim3 grid(gr_cdiv(L, 64), H, B);
-#if GR_SP
-#define QKV_TAIL
-#else
-#define QKV_TAIL , nullptr, 0
-#endif
-  if (head_dim == 128)
-    hipLaunchKernelGGL(qkv_split_kernel<128>, grid, dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k,
-                       (bf16_t*)vt, cosT, sinT, B, H, L, pos0, kv_stride, pos_dev, pos_stride QKV_TAIL);
-  else if (head_dim == 64)
-    hipLaunchKernelGGL(qkv_split_kernel<64>, grid, dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k,
-                       (bf16_t*)vt, cosT, sinT, B, H, L, pos0, kv_stride, pos_dev, pos_stride QKV_TAIL);
-  else return GR_EINVAL;
-#undef QKV_TAIL
-  GR_CHECK_LAUNCH();
-  return GR_OK;
+  return qkv_split_launch<false, false>(dim3(gr_cdiv(L, 64), H, B), stream, head_dim, qkv, q, k, vt, cosT, sinT, B, H, L, pos0, kv_stride,
+                                        pos_dev, pos_stride, nullptr, 0);
 }
 
 // The decode step's RoPE + K / V^T write (L = 1) into a paged cache (kv_layout.h: k_pool and vt_pool are the page pools, block_table
@@ -207,18 +215,8 @@ extern "C" int gr_qkv_split_paged(const void* qkv, void* q, void* k_pool, void* 
   if (!qkv || !k_pool || !vt_pool || !block_table || B <= 0 || H <= 0 || L != 1) return GR_EINVAL;
   if ((cosT == nullptr) != (sinT == nullptr) || table_ld <= 0 || table_ld > 128) return GR_EINVAL;
   if (!pos_dev && (pos0 < 0 || pos0 >= table_ld * KV_PAGE)) return GR_EINVAL;
-#if !GR_SP
-  dim3 grid(1, H, B);
-  if (head_dim == 128)
-    hipLaunchKernelGGL((qkv_split_kernel<128, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k_pool,
-                       (bf16_t*)vt_pool, cosT, sinT, B, H, 1, pos0, 64, pos_dev, pos_stride, block_table, table_ld);
-  else if (head_dim == 64)
-    hipLaunchKernelGGL((qkv_split_kernel<64, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k_pool,
-                       (bf16_t*)vt_pool, cosT, sinT, B, H, 1, pos0, 64, pos_dev, pos_stride, block_table, table_ld);
-  else return GR_EINVAL;
-  GR_CHECK_LAUNCH();
-#endif
-  return GR_OK;
+  return qkv_split_launch<true, false>(dim3(1, H, B), stream, head_dim, qkv, q, k_pool, vt_pool, cosT, sinT, B, H, 1, pos0, 64, pos_dev,
+                                       pos_stride, block_table, table_ld);
 }
 
 // The K / V^T write of a multi-position prefill (L positions per row, rows of the fused QKV buffer [B*L, 3*H*hd]) into a paged cache:
@@ -233,17 +231,8 @@ extern "C" int gr_kv_append_paged(const void* qkv, void* k_pool, void* vt_pool, 
   if ((cosT == nullptr) != (sinT == nullptr) || table_ld <= 0 || table_ld > 128) return GR_EINVAL;
   if (!pos_dev && (pos0 < 0 || pos0 + L > table_ld * KV_PAGE)) return GR_EINVAL;
   if (head_dim != 128 && head_dim != 64) return GR_EINVAL;
-#if !GR_SP
-  dim3 grid(gr_cdiv(L, 64), H, B);
-  if (head_dim == 128)
-    hipLaunchKernelGGL((qkv_split_kernel<128, true, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, nullptr, (bf16_t*)k_pool,
-                       (bf16_t*)vt_pool, cosT, sinT, B, H, L, pos0, KV_PAGE, pos_dev, pos_stride, block_table, table_ld);
-  else
-    hipLaunchKernelGGL((qkv_split_kernel<64, true, true>), grid, dim3(256), 0, stream, (const bf16_t*)qkv, nullptr, (bf16_t*)k_pool,
-                       (bf16_t*)vt_pool, cosT, sinT, B, H, L, pos0, KV_PAGE, pos_dev, pos_stride, block_table, table_ld);
-  GR_CHECK_LAUNCH();
-#endif
-  return GR_OK;
+  return qkv_split_launch<true, true>(dim3(gr_cdiv(L, 64), H, B), stream, head_dim, qkv, nullptr, k_pool, vt_pool, cosT, sinT, B, H, L,
+                                      pos0, KV_PAGE, pos_dev, pos_stride, block_table, table_ld);
 }
 
 // ---------------------------------------------------------------------------------------
